@@ -4,12 +4,18 @@ clip + AdamW) for CoRal's `model=wav2vec2-large` (XLS-R-2B shape) on synthetic 1
 8 x 10 s utterances per GPU, bf16 MFMA compute / fp32 master weights.  BASELINE.json configs[1]
 (N=1) and configs[2] (N=8, weak scaling).
 
-    python bench.py --gpus 1 --steps 8 --warmup 3
+    python bench.py --gpus 1 --steps 8 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/unit/... plus
-  roofline     — dominant GEMM template, live hipEvent timing through ca_prof_begin/end
-  cpu_baseline — the oracle (oracle/wav2vec2_ref.py) timed on this box's host cores (N=1 only)
+Prints ONE JSON line on rank 0: metric/value/unit/ms_per_step/... of the headline.  A plain run does only that: set-up,
+`--warmup` untimed and `--steps` timed steps, the line.  `--full` adds everything else, each measured after the headline:
+  roofline     — dominant GEMM template, live hipEvent timing through ca_prof_begin/end (two extra profiled steps)
+  config.fwd_bwd / config.fp32_matrix_gradients — the same step without the optimiser / on the fp32 gradient route
+  config.also* — the secondary workloads (N=1, wav2vec2-large); config.also_zero2 — the sharded optimiser (N>1)
+  cpu_baseline — the oracle (oracle/wav2vec2_ref.py) timed on the host cores (N=1 only)
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32 / float64, 64 MB at most).
+`--model whisper-* --decode` keeps its per-token time (config.ms_per_token, two more timed generation lengths) without
+`--full`: it is that workload's headline figure (BASELINE.json configs[3]).
 """
 
 from __future__ import annotations
@@ -29,6 +35,39 @@ ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
 
 MFMA_BF16_DENSE_PEAK_TFLOPS = 2500.0  # /opt/skills/guides/MI355X_MICROARCH.md: ~2.5 PF dense (spec)
+DUMP_PARAM_SAMPLE = 1 << 22   # --dump-outputs: fp32 master weights sampled (16 MB per array)
+DUMP_SAMPLE_SEED = 4243
+DUMP_MAX_BYTES = 64 << 20
+
+
+def param_sample_index(trainer, device):
+    """--dump-outputs: a fixed, seeded sample of the trainable fp32 master weights (sorted flat offsets, the same for
+    every run of one model); None where the master is sharded over the ranks (zero_stage 2: a rank keeps only its
+    own slice up to date)."""
+    if trainer is None or getattr(trainer, "zero", False):
+        return None
+    lo, hi = trainer.train_range
+    g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+    idx = torch.randint(lo, hi, (min(DUMP_PARAM_SAMPLE, hi - lo),), generator=g, dtype=torch.int64)
+    return idx.sort().values.to(device)
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy - floating point as float32 (float64 stays float64), integers
+    as float64 (exact) - at most DUMP_MAX_BYTES in all."""
+    import numpy as np
+
+    conv = {}
+    for name, a in arrays.items():
+        t = torch.as_tensor(a).detach().cpu()
+        conv[name] = t.to(torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64).numpy()
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}")
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in conv.items():
+        np.save(d / f"{name}.npy", a)
 
 
 def fwd_gflop_per_utt(shape, T: int, conv_lens) -> float:
@@ -253,9 +292,11 @@ def check_replicas(eng, trainer, rank, extra=None):
     assert all(x == 0.0 for x in spreads.values()), f"replicas diverged: {spreads}"
 
 
-def whisper_measure(model, args, world, rank, device, decode=False, fp8=False, B=None, steps=None, warmup=None):
+def whisper_measure(model, args, world, rank, device, decode=False, fp8=False, B=None, steps=None, warmup=None,
+                    dump_dir=None):
     """One Whisper workload: teacher-forced finetune step on 30 s clips (log-mel on the GPU inside the step) or greedy
-    decoding (`decode`).  -> dict(ms_per_step, value, ...) on every rank."""
+    decoding (`decode`).  -> dict(ms_per_step, value, ...) on every rank.  `dump_dir`: rank 0 writes what the last
+    timed step returned (loss | generated ids) and, for training, a sample of the updated weights (write_outputs)."""
     from coral_amd.trainer import DataParallelTrainer
 
     B = B or args.batch
@@ -282,17 +323,36 @@ def whisper_measure(model, args, world, rank, device, decode=False, fp8=False, B
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
+    last = [None]
+
     def timed(n, **kw):
         sync()
         t0 = time.perf_counter()
         for _ in range(n):
-            step(**kw)
+            last[0] = step(**kw)
         sync()
         return (time.perf_counter() - t0) / n
 
     for _ in range(warmup):
         step()
+    idx = before = None
+    if dump_dir is not None:  # (outside the timed region: the weights before the timed steps, at the sampled offsets)
+        idx = param_sample_index(trainer, device)
+        if idx is not None:
+            trainer.finish()
+            before = eng.store.p32[idx].clone()
     dt = timed(steps)
+    if dump_dir is not None and rank == 0:
+        if decode:
+            outs = {"generated_ids": torch.tensor(last[0])}
+        else:
+            outs = {"loss": last[0]}
+            if idx is not None:
+                trainer.finish()
+                after = eng.store.p32[idx]
+                outs.update(grad_norm=torch.tensor([trainer.grad_norm()], dtype=torch.float64),
+                            params_sample=after, params_update_sample=after - before)
+        write_outputs(dump_dir, outs)
     res = dict(ms_per_step=dt * 1e3, value=world * B * 30.0 / dt, B=B, label_len=int(labels.shape[1]),
                dropout=eng.dropout, activation_dropout=eng.activation_dropout, engine=eng, shape=shape, trainer=trainer)
     if decode:
@@ -314,7 +374,7 @@ def whisper_measure(model, args, world, rank, device, decode=False, fp8=False, B
 def whisper_bench(args, world, rank, device):
     """Secondary workload (BASELINE.json configs[3]/[4] shapes): `--model whisper-*` [--decode] [--fp8-forward]."""
     fp8 = (args.decode and args.fp8_encoder) or (args.fp8_forward and not args.decode)
-    r = whisper_measure(args.model, args, world, rank, device, decode=args.decode, fp8=fp8)
+    r = whisper_measure(args.model, args, world, rank, device, decode=args.decode, fp8=fp8, dump_dir=args.dump_outputs)
     eng, B = r["engine"], r["B"]
     if rank == 0:
         mode = f"greedy decode, {args.decode_tokens} new tokens" if args.decode else "finetune step fwd+bwd+clip+AdamW, teacher-forced"
@@ -340,9 +400,11 @@ def whisper_bench(args, world, rank, device):
         torch.distributed.destroy_process_group()
 
 
-def run_w2v2(model_key, args, world, rank, device, roofline: bool):
+def run_w2v2(model_key, args, world, rank, device, roofline: bool, dump_dir=None):
     """Build the engine for one CoRal model key, run `--warmup` untimed and `--steps` timed finetune steps; with
-    `roofline`, two more steps with every GEMM launch bracketed by hipEvents on its stream."""
+    `roofline` (--full), the forward+backward-only and fp32-gradient timings and two more steps with every GEMM launch
+    bracketed by hipEvents on its stream.  `dump_dir`: rank 0 writes what the last timed step computed, before anything
+    else runs (write_outputs)."""
     import numpy as np
 
     from coral_amd import ops, specaugment
@@ -392,12 +454,32 @@ def run_w2v2(model_key, args, world, rank, device, roofline: bool):
 
     for _ in range(args.warmup):
         loss = trainer.train_step(make_step_batch())
+    idx = before = None
+    if dump_dir is not None:  # (outside the timed region: the weights before the timed steps, at the sampled offsets)
+        idx = param_sample_index(trainer, device)
+        if idx is not None:
+            trainer.finish()
+            before = eng.store.p32[idx].clone()
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = trainer.train_step(make_step_batch())
     sync()
     dt = time.perf_counter() - t0
+    if dump_dir is not None and rank == 0:
+        # what a caller of the step receives (the loss) and what the step computed on the way (the logits of its forward,
+        # the gradient norm it clipped by) or left behind (the updated master weights and the timed steps' update)
+        trainer.finish()
+        # The logits of the last forward stay in the engine's workspace until the next forward: only the lm_head GEMM
+        # writes w["logits"] (the backward reads it and writes w["dlogits"]), the same buffer greedy_decode() reads as
+        # "the logits of the last forward" (coral_amd/wav2vec2.py)
+        w = eng._saved["w"]
+        outs = {"loss": loss, "logits": w["logits"].view(B, T, w["Vp"])[:, :, :shape.vocab_size],
+                "grad_norm": torch.tensor([trainer.grad_norm()], dtype=torch.float64)}
+        if idx is not None:
+            after = eng.store.p32[idx]
+            outs.update(params_sample=after, params_update_sample=after - before)
+        write_outputs(dump_dir, outs)
     tmax = torch.tensor([dt], dtype=torch.float64, device=device)
     if world > 1:
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
@@ -513,7 +595,9 @@ def main():
                     help="feed every step from raw int16 PCM in host memory through the device input pipeline "
                          "(pinned staging + side-stream H2D + on-GPU normalisation): the PCIe-inclusive rate")
     ap.add_argument("--gemm-breakdown", action="store_true", help="print the per-kernel GEMM timing table to stderr")
-    ap.add_argument("--decode", action="store_true", help="whisper models: time greedy decoding instead of training")
+    ap.add_argument("--decode", action="store_true",
+                    help="whisper models: time greedy decoding instead of training; the line also carries the per-token "
+                         "time (config.ms_per_token, from two more timed generation lengths), with or without --full")
     ap.add_argument("--decode-tokens", type=int, default=32)
     ap.add_argument("--fp8-forward", action="store_true",
                     help="whisper finetune step: encoder forward projections and the fc2 / out_proj data gradients in fp8 (DESIGN.md 4.4)")
@@ -533,6 +617,13 @@ def main():
     ap.add_argument("--ragged", action="store_true",
                     help="utterance lengths ~ U[1 s, --seconds] padded to --seconds (the regime of "
                          "R/config/asr_finetuning.yaml:31-32): masked attention / CTC lengths / SpecAugment on valid frames")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else: roofline (profiled steps), config.fwd_bwd, "
+                         "config.fp32_matrix_gradients, the secondary workloads (config.also*), the CPU baseline, and at "
+                         "N>1 without --zero-stage the sharded optimiser (config.also_zero2); the --no-* options narrow it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, "
+                         "64 MB at most; the weights as a fixed, seeded sample)")
     ap.add_argument("--no-also", action="store_true", help="skip the secondary measurements (config.also*)")
     ap.add_argument("--no-fwd-bwd", action="store_true", help="skip the extra forward+backward-only timing (profile runs)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for 1-GPU debugging of the N>1 logic)")
@@ -553,7 +644,7 @@ def main():
     # layer bucket (configs[2]; accelerate/accelerator.py:1892,2053) - and the sharded optimiser (the reference's
     # production launch, `accelerate launch --zero-stage 2`, R/makefile:79-84) is measured right after it in the same
     # process group and reported beside it as config.also_zero2.
-    both_stages = args.zero_stage is None and world > 1 and not args.model.startswith("whisper")
+    both_stages = args.full and args.zero_stage is None and world > 1 and not args.model.startswith("whisper")
     if args.zero_stage is None:
         args.zero_stage = 0
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -582,14 +673,12 @@ def main():
     if args.model.startswith("whisper"):
         return whisper_bench(args, world, rank, device)
 
-    res = run_w2v2(args.model, args, world, rank, device, roofline=True)
+    res = run_w2v2(args.model, args, world, rank, device, roofline=args.full, dump_dir=args.dump_outputs)
     eng, loss_val, trainer_ = res.pop("engine"), res["loss"], res.pop("trainer")
-    if rank == 0:
-        shape, B, T = res["shape"], res["B"], res["T"]
+    if rank == 0 and "prof" in res:  # (--full)
         dom, prof = res["dom"], res["prof"]
         tot_ms = sum(r["ms"] for r in prof)
         tot_fl = sum(r["flops"] for r in prof)
-        step_ms = res["ms_per_step"]
         ach = dom["flops"] / (dom["ms"] * 1e-3) / 1e12 if dom["ms"] > 0 else 0.0
         traffic, traffic_source = None, None
         pmc = ROOT / "profiles" / "pmc_traffic.json"
@@ -599,6 +688,9 @@ def main():
                 traffic_source = "profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, FETCH_SIZE x2 for gfx950; static table, not re-measured in this run)"
             except Exception:
                 traffic = None
+    if rank == 0:
+        shape, B, T = res["shape"], res["B"], res["T"]
+        step_ms = res["ms_per_step"]
         wire = f"{args.grad_wire} wire" if world > 1 else "no collective (1 rank)"
         out = {
             "metric": "audio-seconds/sec (CTC finetune step: fwd+bwd+allreduce+clip+AdamW), wav2vec2-large, 10 s utterances",
@@ -632,19 +724,20 @@ def main():
                            res["step_tflop"] / (res["fwd_bwd"]["ms_per_step"] * 1e-3) / MFMA_BF16_DENSE_PEAK_TFLOPS, 4))}
                           if "fwd_bwd" in res else {}),
                        **({"fp32_matrix_gradients": res["fp32_matrix_gradients"]} if "fp32_matrix_gradients" in res else {})},
-            "roofline": {"bound": "mfma", "kernel": dom["kernel"], "achieved": round(ach, 1),
-                         "timing": "hipEvents around every launch of two extra steps run with all kernels on one stream "
-                                   "(the timed steps overlap the optimiser and the weight gradients on side streams)",
-                         "peak": MFMA_BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(ach / MFMA_BF16_DENSE_PEAK_TFLOPS, 4), "traffic": traffic,
-                         "traffic_source": traffic_source,
-                         "launches": dom["count"] // 2, "avg_us": round(dom["ms"] * 1e3 / max(1, dom["count"]), 2),
-                         "all_gemm_tflops": round(tot_fl / (tot_ms * 1e-3) / 1e12, 1) if tot_ms else 0.0,
-                         "gemm_ms_per_step": round(tot_ms / 2, 2),
-                         "step_algorithmic_tflop": round(res["step_tflop"], 2),
-                         "step_frac_of_peak": round(res["step_tflop"] / (step_ms * 1e-3) / MFMA_BF16_DENSE_PEAK_TFLOPS, 4)},
         }
-    if world == 1 and not args.no_also and args.model == "wav2vec2-large":
+        if "prof" in res:  # (--full)
+            out["roofline"] = {"bound": "mfma", "kernel": dom["kernel"], "achieved": round(ach, 1),
+                               "timing": "hipEvents around every launch of two extra steps run with all kernels on one stream "
+                                         "(the timed steps overlap the optimiser and the weight gradients on side streams)",
+                               "peak": MFMA_BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s",
+                               "frac": round(ach / MFMA_BF16_DENSE_PEAK_TFLOPS, 4), "traffic": traffic,
+                               "traffic_source": traffic_source,
+                               "launches": dom["count"] // 2, "avg_us": round(dom["ms"] * 1e3 / max(1, dom["count"]), 2),
+                               "all_gemm_tflops": round(tot_fl / (tot_ms * 1e-3) / 1e12, 1) if tot_ms else 0.0,
+                               "gemm_ms_per_step": round(tot_ms / 2, 2),
+                               "step_algorithmic_tflop": round(res["step_tflop"], 2),
+                               "step_frac_of_peak": round(res["step_tflop"] / (step_ms * 1e-3) / MFMA_BF16_DENSE_PEAK_TFLOPS, 4)}
+    if args.full and world == 1 and not args.no_also and args.model == "wav2vec2-large":
         # SURVEY.md §0 decision 2: CoRal's `wav2vec2-large` key is the XLS-R-2B shape; the architecture most readers
         # call "wav2vec2-large" (24 L / 1024 / 4096) is CoRal's `wav2vec2-small` key: report it beside the headline.
         del res, eng
@@ -772,7 +865,7 @@ def main():
             if watchdog is not None:
                 watchdog.cancel()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         lock = locals().get("emit_lock")
         if lock is None:

@@ -1,4 +1,4 @@
-"""Turn gpurun_out/prof_<tag>_{stats,fetch,write} (tools/profile_bench.sh) into committed files:
+"""Turn $PROF_OUT/prof_<tag>_{stats,fetch,write} (tools/profile_bench.sh; PROF_OUT defaults to prof_out) into committed files:
 profiles/<tag>_kernel_stats.csv (rocprofv3 --kernel-trace --stats summary, verbatim columns) and
 profiles/pmc_traffic.json (kernel symbol -> HBM bytes per launch = 2*FETCH_SIZE + WRITE_SIZE KiB,
 the gfx950 correction of /opt/skills/guides/MI355X_MICROARCH.md §HBM)."""
@@ -6,17 +6,18 @@ import collections
 import csv
 import glob
 import json
+import os
 import sys
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
 nsteps = int(sys.argv[2]) if len(sys.argv) > 2 else 8
-cmd = sys.argv[3] if len(sys.argv) > 3 else "python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-also --no-fwd-bwd"
+cmd = sys.argv[3] if len(sys.argv) > 3 else "python bench.py --steps 4 --warmup 2 --full --no-cpu-baseline --no-also --no-fwd-bwd"
 
 
 def one(pattern):
-    f = glob.glob(str(ROOT / "gpurun_out" / pattern))
+    f = glob.glob(str(ROOT / os.environ.get("PROF_OUT", "prof_out") / pattern))
     return max(f, key=lambda p: Path(p).stat().st_mtime) if f else None
 
 
@@ -67,7 +68,7 @@ if sq:
         agg[r["Kernel_Name"]][r["Counter_Name"]].append(float(r["Counter_Value"]))
     names = ["SQ_VALU_MFMA_BUSY_CYCLES", "SQ_BUSY_CYCLES", "SQ_WAVE_CYCLES", "SQ_INSTS_VALU", "SQ_INSTS_MFMA", "SQ_WAIT_ANY",
              "SQ_WAIT_INST_ANY", "GRBM_GUI_ACTIVE"]
-    out_lines = ["# rocprofv3 --pmc " + " ".join(names) + " -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-also --no-fwd-bwd",
+    out_lines = ["# rocprofv3 --pmc " + " ".join(names) + " -- python bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-also --no-fwd-bwd",
                  "# per-launch averages over the launches of the run; SQ_*_CYCLES of waves are quad-cycles, SQ_VALU_MFMA_BUSY_CYCLES and",
                  "# GRBM_GUI_ACTIVE are cycles summed over the 8 XCDs (MI355X_MICROARCH.md, cycle constants); mfma_busy_frac =",
                  "# SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 * 1024 SIMDs) = share of the kernel's cycles its matrix pipes were busy",

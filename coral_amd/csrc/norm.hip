@@ -313,12 +313,17 @@ static int ln_bwd_grid(int64_t rows, int C) {
   return (int)g;
 }
 
-template <int NCH, bool ACT, bool DPP, bool XF32 = false>
+// DROP: a second output dxd = dropout(dx; drop_p, drop_seed) of the bf16-rounded dx, element (row, col) decided from
+// (seed, row * C + col) - bit for bit what ca_dropout_bf16 makes of dx.  The wav2vec2 backward needs the gradient entering
+// a sub-layer whose output went through hidden-state dropout both as it is (the residual stream) and masked (the
+// sub-layer's data and weight gradients); each comes out of a LayerNorm backward.
+template <int NCH, bool ACT, bool DPP, bool XF32 = false, bool DROP = false>
 __global__ __launch_bounds__(256, 2) void ln_bwd_kernel(
     const unsigned short* __restrict__ dy, const void* __restrict__ x,
     const float* __restrict__ gamma, const float* __restrict__ beta,
     const float* __restrict__ stats, const unsigned short* __restrict__ dres,
-    unsigned short* __restrict__ dx, float* __restrict__ partial, int64_t rows, int C) {
+    unsigned short* __restrict__ dx, float* __restrict__ partial, int64_t rows, int C,
+    unsigned short* __restrict__ dxd, float drop_p, uint64_t drop_seed) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* red = (float*)smem_raw;  // [4 waves][2][C]
   const int lane = threadIdx.x & 63;
@@ -439,6 +444,15 @@ __global__ __launch_bounds__(256, 2) void ln_bwd_kernel(
           o[e] = f2bf(crstd * (du * g8[e] - m1 - h * m2) + bf2f(cr[c][e]));
         }
         *(u16x8_t*)(dxr + ch * 8) = o;
+        if constexpr (DROP) {
+          const uint64_t i8 = (uint64_t)row * C + ch * 8;
+          const unsigned int keep = ca_dropout_keep4(drop_seed, i8, drop_p) | (ca_dropout_keep4(drop_seed, i8 + 4, drop_p) << 4);
+          const float ks = 1.f / (1.f - drop_p);
+          u16x8_t od;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) od[e] = ((keep >> e) & 1u) ? f2bf(bf2f(o[e]) * ks) : (unsigned short)0;
+          *(u16x8_t*)(dxd + row * C + ch * 8) = od;
+        }
       }
     }
     if constexpr (PIPE) {
@@ -554,10 +568,10 @@ extern "C" int64_t ca_layernorm_bwd_partial_floats(int64_t rows, int32_t C) {
   return (int64_t)ln_bwd_grid(rows, C) * 2 * C;
 }
 
-extern "C" int ca_layernorm_bwd_ex(const void* dy, const void* x, const float* gamma,
-                                   const float* beta, const float* stats, const void* dres,
-                                   void* dx, float* dgamma, float* dbeta, float* partial,
-                                   int64_t rows, int32_t C, int32_t act, int32_t x_f32, void* stream) {
+static int ln_bwd_launch(const void* dy, const void* x, const float* gamma, const float* beta, const float* stats,
+                         const void* dres, void* dx, void* dxd, float drop_p, uint64_t drop_seed, float* dgamma,
+                         float* dbeta, float* partial, int64_t rows, int32_t C, int32_t act, int32_t x_f32,
+                         void* stream) {
   CA_CHECK_ARG(dy && x && gamma && stats && dx && partial, "ca_layernorm_bwd: null pointer");
   CA_CHECK_ARG(!x_f32 || C <= 1024, "ca_layernorm_bwd_ex: fp32 rows are served up to C = 1024 (C=%d)", C);
   CA_CHECK_ARG(!act || beta, "ca_layernorm_bwd: act needs beta");
@@ -568,26 +582,30 @@ extern "C" int ca_layernorm_bwd_ex(const void* dy, const void* x, const float* g
   dim3 grid(g), block(256);
   const size_t lds = (size_t)4 * 2 * C * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
-#define LN_BWD_(N, A, D)                                                                              \
+#define LN_BWD_(N, A, D, R)                                                                           \
   do {                                                                                                \
     if (x_f32 && N <= 2)                                                                              \
-      hipLaunchKernelGGL((ln_bwd_kernel<(N <= 2 ? N : 1), A, D, true>), grid, block, lds, s,          \
+      hipLaunchKernelGGL((ln_bwd_kernel<(N <= 2 ? N : 1), A, D, true, R>), grid, block, lds, s,       \
                          (const unsigned short*)dy, x, gamma, beta, stats, (const unsigned short*)dres, \
-                         (unsigned short*)dx, partial, rows, C);                                      \
+                         (unsigned short*)dx, partial, rows, C, (unsigned short*)dxd, drop_p, drop_seed); \
     else                                                                                              \
-      hipLaunchKernelGGL((ln_bwd_kernel<N, A, D, false>), grid, block, lds, s,                        \
+      hipLaunchKernelGGL((ln_bwd_kernel<N, A, D, false, R>), grid, block, lds, s,                     \
                          (const unsigned short*)dy, x, gamma, beta, stats, (const unsigned short*)dres, \
-                         (unsigned short*)dx, partial, rows, C);                                      \
+                         (unsigned short*)dx, partial, rows, C, (unsigned short*)dxd, drop_p, drop_seed); \
   } while (0)
   static const int use_dpp = [] { const char* e = getenv("CA_LN_BWD_DPP"); return e ? atoi(e) : 1; }();
-#define LN_BWD(N)                \
-  do {                           \
-    if (act)                     \
-      LN_BWD_(N, true, true);    \
-    else if (use_dpp)            \
-      LN_BWD_(N, false, true);   \
-    else                         \
-      LN_BWD_(N, false, false);  \
+#define LN_BWD(N)                          \
+  do {                                     \
+    if (act)                               \
+      LN_BWD_(N, true, true, false);       \
+    else if (dxd && use_dpp)               \
+      LN_BWD_(N, false, true, true);       \
+    else if (dxd)                          \
+      LN_BWD_(N, false, false, true);      \
+    else if (use_dpp)                      \
+      LN_BWD_(N, false, true, false);      \
+    else                                   \
+      LN_BWD_(N, false, false, false);     \
   } while (0)
   switch (nch) {
     case 1: LN_BWD(1); break;
@@ -608,11 +626,27 @@ extern "C" int ca_layernorm_bwd_ex(const void* dy, const void* x, const float* g
   CA_CHECK_LAUNCH("ca_layernorm_bwd(reduce)");
   return CA_OK;
 }
+extern "C" int ca_layernorm_bwd_ex(const void* dy, const void* x, const float* gamma,
+                                   const float* beta, const float* stats, const void* dres,
+                                   void* dx, float* dgamma, float* dbeta, float* partial,
+                                   int64_t rows, int32_t C, int32_t act, int32_t x_f32, void* stream) {
+  return ln_bwd_launch(dy, x, gamma, beta, stats, dres, dx, nullptr, 0.f, 0, dgamma, dbeta, partial, rows, C, act, x_f32,
+                       stream);
+}
 extern "C" int ca_layernorm_bwd(const void* dy, const void* x, const float* gamma,
                                 const float* beta, const float* stats, const void* dres,
                                 void* dx, float* dgamma, float* dbeta, float* partial,
                                 int64_t rows, int32_t C, int32_t act, void* stream) {
   return ca_layernorm_bwd_ex(dy, x, gamma, beta, stats, dres, dx, dgamma, dbeta, partial, rows, C, act, 0, stream);
+}
+extern "C" int ca_layernorm_bwd_dropout(const void* dy, const void* x, const float* gamma, const float* beta,
+                                        const float* stats, const void* dres, void* dx, void* dx_drop, float p,
+                                        uint64_t seed, float* dgamma, float* dbeta, float* partial, int64_t rows,
+                                        int32_t C, int32_t x_f32, void* stream) {
+  CA_CHECK_ARG(dx_drop != nullptr && dx_drop != dx, "ca_layernorm_bwd_dropout: dx_drop must be its own buffer");
+  CA_CHECK_ARG(p >= 0.f && p < 1.f, "ca_layernorm_bwd_dropout: bad p");
+  return ln_bwd_launch(dy, x, gamma, beta, stats, dres, dx, dx_drop, p, seed, dgamma, dbeta, partial, rows, C, 0, x_f32,
+                       stream);
 }
 
 // ---- column sums (bias gradients) ---------------------------------------------------------

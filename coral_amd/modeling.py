@@ -1,6 +1,10 @@
 """HF-shaped model objects over the engines: `Wav2Vec2ForCTC.from_pretrained / save_pretrained`,
 `model(input_values, attention_mask, labels)` -> output with `.loss` / `.logits`
-(the contract `Trainer` and the ASR pipeline rely on)."""
+(the contract `Trainer` and the ASR pipeline rely on).
+
+The five dropouts CoRal passes to `from_pretrained` (activation, attention, hidden, feat_proj and final dropout) are
+all implemented by the engine, in training mode only (resolve_dropouts: argument, else the checkpoint's config.json,
+else 0.0).  `feat_quantizer_dropout` is accepted and has no effect, as in HF: `Wav2Vec2ForCTC` has no quantizer."""
 
 from __future__ import annotations
 
@@ -13,7 +17,7 @@ import torch
 
 from . import specaugment
 from .autograd import attach_backward
-from .wav2vec2 import CORAL_W2V2_SHAPES, Wav2Vec2CTCEngine, Wav2Vec2Shape
+from .wav2vec2 import CORAL_W2V2_SHAPES, DROPOUT_KEYS, Wav2Vec2CTCEngine, Wav2Vec2Shape
 
 logger = logging.getLogger(__package__)
 
@@ -54,15 +58,38 @@ def load_checkpoint_tensors(model_dir: Path) -> dict:
     raise FileNotFoundError(f"{model_dir} holds neither model.safetensors nor pytorch_model.bin")
 
 
-def _warn_unsupported_dropouts(overrides: dict, cfg: dict):
-    """The reference passes five dropouts to `from_pretrained` (R/src/coral/wav2vec2.py:108-112); every CoRal model
-    YAML sets all but `activation_dropout` to 0.  The engine implements activation dropout only (the FFN GEMM's
-    epilogue): a non-zero value for one of the others must not pass silently."""
-    for k in ("attention_dropout", "hidden_dropout", "feat_proj_dropout", "final_dropout"):
-        v = float(overrides.get(k, 0.0) or 0.0)  # the checkpoint's own config values only matter in training
-        if v != 0.0:
-            raise NotImplementedError(f"{k}={v}: only activation_dropout is implemented on the MI355X engine "
-                                      "(every CoRal wav2vec2 config sets the other dropouts to 0.0)")
+def resolve_dropouts(overrides: dict, cfg: dict | None = None) -> dict:
+    """The five dropouts the reference passes to `from_pretrained` (R/src/coral/wav2vec2.py:108-112) -> {key: p}.
+
+    Each one is the explicit argument if given (not None), otherwise the checkpoint's `config.json` value (cfg; {} or
+    None for a hub name without a local directory), otherwise 0.0 - the precedence of `from_pretrained(**kwargs)` over
+    the stored config.  A value outside [0, 1) raises ValueError."""
+    cfg = cfg or {}
+    out = {}
+    for k in DROPOUT_KEYS:
+        v = overrides.get(k)
+        if v is None:
+            v = cfg.get(k)
+        v = 0.0 if v is None else float(v)
+        if not 0.0 <= v < 1.0:
+            raise ValueError(f"{k}={v}: a dropout probability must lie in [0, 1)")
+        out[k] = v
+    return out
+
+
+def hf_config(s: Wav2Vec2Shape, spec: dict) -> dict:
+    """The `config.json` Wav2Vec2ForCTC.save_pretrained writes (HF Wav2Vec2Config keys) for a shape and the
+    SpecAugment settings."""
+    return dict(architectures=["Wav2Vec2ForCTC"], model_type="wav2vec2", hidden_size=s.hidden_size,
+                num_hidden_layers=s.num_hidden_layers, num_attention_heads=s.num_attention_heads,
+                intermediate_size=s.intermediate_size, conv_dim=list(s.conv_dim), conv_kernel=list(s.conv_kernel),
+                conv_stride=list(s.conv_stride), num_conv_pos_embeddings=s.num_conv_pos_embeddings,
+                num_conv_pos_embedding_groups=s.num_conv_pos_embedding_groups, vocab_size=s.vocab_size,
+                pad_token_id=s.pad_token_id, ctc_loss_reduction=s.ctc_loss_reduction,
+                ctc_zero_infinity=s.ctc_zero_infinity, feat_extract_norm="layer", conv_bias=True,
+                do_stable_layer_norm=True, hidden_act="gelu", feat_extract_activation="gelu",
+                layerdrop=s.layerdrop, layer_norm_eps=s.layer_norm_eps,
+                **{k: float(getattr(s, k)) for k in DROPOUT_KEYS}, **{k: v for k, v in spec.items()})
 
 
 class Wav2Vec2ForCTC:
@@ -86,6 +113,7 @@ class Wav2Vec2ForCTC:
                                               "mask_feature_prob", "mask_feature_length") if k in overrides}
         if path.is_dir() and (path / "config.json").exists():
             cfg = json.loads((path / "config.json").read_text())
+            drops = resolve_dropouts(overrides, cfg)
             shape = Wav2Vec2Shape(
                 hidden_size=cfg["hidden_size"], num_hidden_layers=cfg["num_hidden_layers"],
                 num_attention_heads=cfg["num_attention_heads"], intermediate_size=cfg["intermediate_size"],
@@ -97,8 +125,7 @@ class Wav2Vec2ForCTC:
                 pad_token_id=overrides.get("pad_token_id", cfg["pad_token_id"]),
                 ctc_loss_reduction=overrides.get("ctc_loss_reduction", cfg.get("ctc_loss_reduction", "sum")),
                 ctc_zero_infinity=overrides.get("ctc_zero_infinity", cfg.get("ctc_zero_infinity", True)),
-                activation_dropout=overrides.get("activation_dropout", cfg.get("activation_dropout", 0.0)),
-                layerdrop=overrides.get("layerdrop", cfg.get("layerdrop", 0.0)))
+                layerdrop=overrides.get("layerdrop", cfg.get("layerdrop", 0.0)), **drops)
             model = cls(shape, device, freeze_base, spec)
             rep = model.engine.load_state_dict(load_checkpoint_tensors(path), strict=False, seed=seed)
             if rep["missing"]:
@@ -106,17 +133,15 @@ class Wav2Vec2ForCTC:
             if rep["unexpected"]:
                 logger.info("%s: %d checkpoint tensors not used by Wav2Vec2ForCTC (e.g. %s)", path,
                             len(rep["unexpected"]), rep["unexpected"][0])
-            _warn_unsupported_dropouts(overrides, cfg)
             return model
         if name_or_path not in HUB_SHAPES:
             raise ValueError(f"unknown model {name_or_path!r}: not a local directory and not one of {list(HUB_SHAPES)}")
+        drops = resolve_dropouts(overrides, {})
         shape = Wav2Vec2Shape(**HUB_SHAPES[name_or_path],
                               vocab_size=overrides.get("vocab_size", 46), pad_token_id=overrides.get("pad_token_id", 45),
                               ctc_loss_reduction=overrides.get("ctc_loss_reduction", "sum"),
                               ctc_zero_infinity=overrides.get("ctc_zero_infinity", True),
-                              activation_dropout=overrides.get("activation_dropout", 0.0),
-                              layerdrop=overrides.get("layerdrop", 0.0))
-        _warn_unsupported_dropouts(overrides, {})
+                              layerdrop=overrides.get("layerdrop", 0.0), **drops)
         logger.warning("no network / hub cache here: %s is instantiated with seeded random weights "
                        "(pass a local directory holding model.safetensors for real weights)", name_or_path)
         model = cls(shape, device, freeze_base, spec)
@@ -144,18 +169,7 @@ class Wav2Vec2ForCTC:
         """HF layout: config.json + model.safetensors with HF parameter names."""
         model_dir = Path(model_dir)
         model_dir.mkdir(parents=True, exist_ok=True)
-        s = self.shape
-        cfg = dict(architectures=["Wav2Vec2ForCTC"], model_type="wav2vec2", hidden_size=s.hidden_size,
-                   num_hidden_layers=s.num_hidden_layers, num_attention_heads=s.num_attention_heads,
-                   intermediate_size=s.intermediate_size, conv_dim=list(s.conv_dim), conv_kernel=list(s.conv_kernel),
-                   conv_stride=list(s.conv_stride), num_conv_pos_embeddings=s.num_conv_pos_embeddings,
-                   num_conv_pos_embedding_groups=s.num_conv_pos_embedding_groups, vocab_size=s.vocab_size,
-                   pad_token_id=s.pad_token_id, ctc_loss_reduction=s.ctc_loss_reduction,
-                   ctc_zero_infinity=s.ctc_zero_infinity, feat_extract_norm="layer", conv_bias=True,
-                   do_stable_layer_norm=True, hidden_act="gelu", feat_extract_activation="gelu",
-                   activation_dropout=s.activation_dropout, layerdrop=s.layerdrop, layer_norm_eps=s.layer_norm_eps,
-                   **{k: v for k, v in self.spec.items()})
-        (model_dir / "config.json").write_text(json.dumps(cfg, indent=2))
+        (model_dir / "config.json").write_text(json.dumps(hf_config(self.shape, self.spec), indent=2))
         sd = self.engine.state_dict()
         if not (float(self.spec.get("mask_time_prob", 0.0)) > 0.0 or float(self.spec.get("mask_feature_prob", 0.0)) > 0.0):
             # HF only creates `masked_spec_embed` when one of the two probabilities is positive

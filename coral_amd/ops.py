@@ -413,6 +413,14 @@ def layernorm_bwd(dy, x, gamma, beta, stats, dres, dx, dgamma, dbeta, partial, r
           "ca_layernorm_bwd")
 
 
+def layernorm_bwd_dropout(dy, x, gamma, beta, stats, dres, dx, dx_drop, p, seed, dgamma, dbeta, partial, rows, Cn):
+    """layernorm_bwd (act = 0) that also writes dx_drop = dropout(dx; p, seed), the mask `dropout` takes for the same seed
+    over the [rows, Cn] matrix (ca_layernorm_bwd_dropout)."""
+    check(lib().ca_layernorm_bwd_dropout(_p(dy), _p(x), _p(gamma), _p(beta), _p(stats), _p(dres), _p(dx), _p(dx_drop),
+                                         float(p), int(seed), _p(dgamma), _p(dbeta), _p(partial), rows, Cn,
+                                         int(x.dtype == torch.float32), _stream()), "ca_layernorm_bwd_dropout")
+
+
 def colsum_partial_floats(rows, N):
     return lib().ca_colsum_partial_floats(rows, N)
 

@@ -49,6 +49,12 @@ class Wav2Vec2Shape:
     ctc_zero_infinity: bool = True
     activation_dropout: float = 0.0
     layerdrop: float = 0.0
+    # the other dropouts of Wav2Vec2Config ($TF/models/wav2vec2/modeling_wav2vec2.py:433,458,571,642,765,1698): training only,
+    # scale 1 / (1 - p); Wav2Vec2CTCEngine.dropout_site gives every site its (p, seed)
+    attention_dropout: float = 0.0
+    hidden_dropout: float = 0.0
+    feat_proj_dropout: float = 0.0
+    final_dropout: float = 0.0
 
     @property
     def head_dim(self):
@@ -200,11 +206,32 @@ class CTCOutput(dict):
         return dict.__getitem__(self, k)
 
 
+DROPOUT_KEYS = ("activation_dropout", "attention_dropout", "hidden_dropout", "feat_proj_dropout", "final_dropout")
+
+# dropout site -> (seed code, Wav2Vec2Shape field).  Sites of HF's stable-LayerNorm Wav2Vec2ForCTC:
+#   feat_proj  after the feature projection, before SpecAugment / padding       ($TF/.../modeling_wav2vec2.py:433)
+#   pos_conv   on h0 + pos_conv(h0) in front of layer 0 (the sum)               (:765)
+#   attention  on the softmax probabilities of layer l                          (:458)
+#   attn_out   on the attention output of layer l before its residual add       (:642)
+#   ffn_out    on the FFN output of layer l before its residual add             (:571)
+#   final      after the encoder's final LayerNorm, before lm_head              (:1698)
+DROPOUT_SITES = {"attention": (1, "attention_dropout"), "attn_out": (2, "hidden_dropout"),
+                 "ffn_out": (3, "hidden_dropout"), "feat_proj": (4, "feat_proj_dropout"),
+                 "pos_conv": (5, "hidden_dropout"), "final": (6, "final_dropout")}
+
+
 class Wav2Vec2CTCEngine:
     """Forward + backward of Wav2Vec2ForCTC as a fixed sequence of HIP kernels."""
 
     def __init__(self, shape: Wav2Vec2Shape, device="cuda:0", freeze_base: bool = False,
                  fused_attention: bool = True):
+        site_p = [float(getattr(shape, k)) for k in {key for _, key in DROPOUT_SITES.values()}]
+        if not all(0.0 <= v < 1.0 for v in site_p):
+            raise ValueError(f"dropout probabilities must lie in [0, 1): {shape}")
+        if not fused_attention and shape.attention_dropout > 0:
+            raise ValueError("attention_dropout needs the fused attention kernels (fused_attention=True)")
+        if shape.num_hidden_layers > 100 and any(site_p):
+            raise ValueError("at most 100 encoder layers with dropout: the seeds of a step give every site a block of 100")
         self.s = shape
         self.fused_attention = fused_attention  # False: batched-GEMM + softmax kernels (A/B reference)
         self.device = torch.device(device)
@@ -385,6 +412,18 @@ class Wav2Vec2CTCEngine:
         self.training = mode
         return self
 
+    def dropout_site(self, site: str, l: int = 0, training: bool | None = None) -> tuple:
+        """(p, seed) of one dropout site (DROPOUT_SITES) of layer l in the current step; (0.0, 0) outside training or
+        with p = 0.  The forward and the backward both ask here, so the backward regenerates the forward's masks.
+
+        Seeds: step_seed * 1000 + 100 * code + l.  The activation dropout of layer l keeps step_seed * 1000 + l, so the
+        sites and layers of one step draw from disjoint seeds (l < 100), and no seed of one step is one of another."""
+        code, key = DROPOUT_SITES[site]
+        p = float(getattr(self.s, key)) if (self.training if training is None else training) else 0.0
+        if p <= 0.0:
+            return 0.0, 0
+        return p, self.step_seed * 1000 + 100 * code + l
+
     def eval(self):
         return self.train(False)
 
@@ -493,6 +532,11 @@ class Wav2Vec2CTCEngine:
             w["dBr"] = [w["dB"], z(M * d), z(M * d)]
             w["dCr"] = [w["dC"], z(M * d)]
             w["dqkvr"] = [w["dqkv"], z(M * 3 * d)]
+            if s.hidden_dropout > 0:
+                # dropout(dh) of the FFN-output site and dropout(dh1) of the attention-output site (hidden dropout): the
+                # second outputs of the LayerNorm backwards, rotating like dBr / dCr (the weight gradients read them)
+                w["dhmr"] = [z(M * d) for _ in range(3)]
+                w["dh1mr"] = [z(M * d) for _ in range(2)]
             if not self.fused_attention:
                 w["dS"] = z(B * H * T * Tp)
             w["du"] = z(M * f)
@@ -581,6 +625,9 @@ class Wav2Vec2CTCEngine:
                           w["xln"], w["fp_stats"], M, C6, eps)
         ops.gemm(w["xln"], p16, w["h0"], M=M, N=d, K=C6, lda=C6, ldb=C6, ldc=d,
                  b_off=o(fp + "projection.weight"), bias=p32, bias_off=o(fp + "projection.bias"))
+        pf = self.dropout_site("feat_proj")
+        if pf[0] > 0:
+            ops.dropout(w["h0"], w["h0"], M * d, *pf)
         # SpecAugment + padding
         # (host-sampled masks and labels go through pinned staging: a pageable .to(device) here would stall the host
         # until the GPU had drained the previous step)
@@ -597,6 +644,9 @@ class Wav2Vec2CTCEngine:
                  lda=Cg, ldb=K * Cg, ldc=d, bias=p32, bias_off=o("wav2vec2.encoder.pos_conv_embed.conv.bias"),
                  epilogue=EPI_GELU_RESIDUAL, batch1=B, batch2=G, sA=(G * Tpad * Cg, Tpad * Cg),
                  sB=(0, Cg * K * Cg), sC=(T * d, Cg), sR=(T * d, Cg), sBias=(0, Cg))
+        pa = self.dropout_site("pos_conv")
+        if pa[0] > 0:  # (hidden dropout on the sum h0 + pos_conv(h0): layer 0 and its LN backward read the dropped values)
+            ops.dropout(w["h"][0], w["h"][0], M * d, *pa)
         # encoder layers
         drop_p = s.activation_dropout if self.training else 0.0
         scale = hd ** -0.5
@@ -611,20 +661,23 @@ class Wav2Vec2CTCEngine:
                               w["x1"][l], w["st1"][l], M, d, eps)
             ops.gemm(w["x1"][l], p16, w["qkv"][l], M=M, N=3 * d, K=d, lda=d, ldb=d, ldc=3 * d,
                      b_off=o(pl + "attention.q_proj.weight"), bias=p32, bias_off=o(pl + "attention.q_proj.bias"))
-            self._attention_fwd(w, l, B, T, Tp, H, hd, d, flen, scale)
+            self._attention_fwd(w, l, B, T, Tp, H, hd, d, flen, scale, self.dropout_site("attention", l))
+            pb = self.dropout_site("attn_out", l)
             ops.gemm(w["ctx"][l], p16, w["h1"][l], M=M, N=d, K=d, lda=d, ldb=d, ldc=d,
                      b_off=o(pl + "attention.out_proj.weight"), bias=p32,
-                     bias_off=o(pl + "attention.out_proj.bias"), epilogue=EPI_RESIDUAL, R=hin, ldr=d)
+                     bias_off=o(pl + "attention.out_proj.bias"), epilogue=EPI_RESIDUAL, R=hin, ldr=d,
+                     dropout_p=pb[0], dropout_seed=pb[1])
             ops.layernorm_fwd(w["h1"][l], st.view(pl + "final_layer_norm.weight"),
                               st.view(pl + "final_layer_norm.bias"), w["x2"][l], w["st2"][l], M, d, eps)
             ops.gemm(w["x2"][l], p16, w["u"][l], C2=w["g"][l], M=M, N=f, K=d, lda=d, ldb=d, ldc=f,
                      b_off=o(pl + "feed_forward.intermediate_dense.weight"), bias=p32,
                      bias_off=o(pl + "feed_forward.intermediate_dense.bias"), epilogue=EPI_GELU,
                      dropout_p=drop_p, dropout_seed=self.step_seed * 1000 + l, stream_out=ops.STREAM_U)
+            pc = self.dropout_site("ffn_out", l)
             ops.gemm(w["g"][l], p16, hout, M=M, N=d, K=f, lda=f, ldb=f, ldc=d,
                      b_off=o(pl + "feed_forward.output_dense.weight"), bias=p32,
                      bias_off=o(pl + "feed_forward.output_dense.bias"), epilogue=EPI_RESIDUAL,
-                     R=w["h1"][l], ldr=d)
+                     R=w["h1"][l], ldr=d, dropout_p=pc[0], dropout_seed=pc[1])
         # final LN + lm_head (fp32 logits, ld = Vp)
         self._await("head")
         for l in range(L):  # dropped layers were not waited for above; the backward reads every layer's weights
@@ -632,13 +685,16 @@ class Wav2Vec2CTCEngine:
                 self._await(f"layer{l}")
         ops.layernorm_fwd(w["h"][L], st.view("wav2vec2.encoder.layer_norm.weight"),
                           st.view("wav2vec2.encoder.layer_norm.bias"), w["hf"], w["stf"], M, d, eps)
+        pz = self.dropout_site("final")
+        if pz[0] > 0:  # in place: lm_head and its weight gradient both read the dropped values
+            ops.dropout(w["hf"], w["hf"], M * d, *pz)
         V = s.vocab_size
         ops.gemm(w["hf"], p16, w["logits"], M=M, N=V, K=d, lda=d, ldb=d, ldc=Vp,
                  b_off=o("lm_head.weight"), bias=p32, bias_off=o("lm_head.bias"))
         logits = w["logits"].view(B, T, Vp)[:, :, :V]
         out = CTCOutput(logits=logits, loss=None)
         self._saved = dict(w=w, x=x, flen=flen, keep=keep, tm=tm, fm=fm, drop_p=drop_p, B=B, N=N,
-                           has_loss=False)
+                           has_loss=False, training=self.training)
         if labels is not None:
             lab = self._stager.to_device(labels, torch.int32, "lab")
             Lmax = lab.shape[1]
@@ -659,12 +715,13 @@ class Wav2Vec2CTCEngine:
             self._saved["has_loss"] = True
         return out
 
-    def _attention_fwd(self, w, l, B, T, Tp, H, hd, d, flen, scale):
+    def _attention_fwd(self, w, l, B, T, Tp, H, hd, d, flen, scale, drop=(0.0, 0)):
         if self.fused_attention:
             qkv = w["qkv"][l]
             ops.attn_fwd(qkv, qkv, qkv, w["ctx"][l], w["lse"][l], B=B, H=H, Tq=T, Tk=T, hd=hd, Tqp=w["Tqp"],
                          scale=scale, ldq=3 * d, ldk=3 * d, ldv=3 * d, ldo=d, sqb=T * 3 * d, skb=T * 3 * d,
-                         svb=T * 3 * d, sob=T * d, q_off=0, k_off=d, v_off=2 * d, klen=flen)
+                         svb=T * 3 * d, sob=T * d, q_off=0, k_off=d, v_off=2 * d, klen=flen, dropout_p=drop[0],
+                         dropout_seed=drop[1])
             return
         qkv, S, P, ctx = w["qkv"][l], w["S"], w["P"][l], w["ctx"][l]
         ops.gemm(qkv, qkv, S, M=T, N=T, K=hd, lda=3 * d, ldb=3 * d, ldc=Tp, b_off=d, alpha=scale,
@@ -718,10 +775,34 @@ class Wav2Vec2CTCEngine:
             return
         ops.gemm(d16, p16, w["dA"], M=M, N=d, K=V, lda=Vp, b_layout=MNMAJOR, ldb=d, ldc=d,
                  b_off=o("lm_head.weight"))
+        tr = sv["training"]
+        pz = self.dropout_site("final", training=tr)
+        if pz[0] > 0:
+            ops.dropout(w["dA"], w["dA"], M * d, *pz)
+
+        def branch_site(j):
+            """(p, seed) of the hidden dropout whose output the residual stream h[j] carries: the FFN-output site of the
+            highest kept layer below j, or the one on h0 + pos_conv(h0) when there is none (dropped layers are the
+            identity and draw no masks)."""
+            below = [k for k in range(j) if keep[k]]
+            return self.dropout_site("ffn_out", below[-1], tr) if below else self.dropout_site("pos_conv", training=tr)
+
+        def ln_bwd(dy, x, ln, stats, dres, dx, dxm, drop, dgamma, dbeta, lpart):
+            """LayerNorm backward; with drop[0] > 0 it also leaves dropout(dx) in dxm (ca_layernorm_bwd_dropout)."""
+            if drop[0] > 0:
+                ops.layernorm_bwd_dropout(dy, x, st.view(ln), None, stats, dres, dx, dxm, drop[0], drop[1], dgamma, dbeta,
+                                          lpart, M, d)
+            else:
+                ops.layernorm_bwd(dy, x, st.view(ln), None, stats, dres, dx, dgamma, dbeta, lpart, M, d)
+
         dh = w["dB"]
-        ops.layernorm_bwd(w["dA"], w["h"][L], st.view("wav2vec2.encoder.layer_norm.weight"), None,
-                          w["stf"], None, dh, st.view("wav2vec2.encoder.layer_norm.weight", "g32"),
-                          st.view("wav2vec2.encoder.layer_norm.bias", "g32"), part, M, d)
+        # dhm: dropout(dh) with the mask of the hidden-dropout site whose output dh is the gradient of (None: no such
+        # dropout); the gradient of that site's branch, while dh itself carries on down the residual stream
+        drop = branch_site(L)
+        dhm = w["dhmr"][0] if drop[0] > 0 else None
+        ln_bwd(w["dA"], w["h"][L], "wav2vec2.encoder.layer_norm.weight", w["stf"], None, dh, dhm, drop,
+               st.view("wav2vec2.encoder.layer_norm.weight", "g32"), st.view("wav2vec2.encoder.layer_norm.bias", "g32"),
+               part)
         done("head")
         # dh = gradient wrt residual stream leaving layer L-1
         other = w["dA"]
@@ -779,15 +860,21 @@ class Wav2Vec2CTCEngine:
                 if it - 2 in wdone:
                     main.wait_event(wdone.pop(it - 2))
                 dh_next, du, dh1, dqkv = w["dBr"][(it + 1) % 3], w["dur"][it & 1], w["dCr"][it & 1], w["dqkvr"][it & 1]
+                mi, m1 = (it + 1) % 3, it & 1
             else:
                 dh_next, du, dh1, dqkv = dh, w["du"], w["dC"], w["dqkv"]
+                mi, m1 = 0, 0
+            drop_o, drop_n = self.dropout_site("attn_out", l, tr), branch_site(l)
+            dh1m = w["dh1mr"][m1] if drop_o[0] > 0 else None
+            dhm_next = w["dhmr"][mi] if drop_n[0] > 0 else None
+            dy2 = dh if dhm is None else dhm  # gradient of the FFN output (before hidden dropout)
             # FFN2: h_out = h1 + W2 g + b2
             # (bias gradients = column sums of the same dY: taken inside the weight-gradient kernel where it runs
             # on the 256x256 tiles, see ops.wgrad_gemm)
-            wg = [dict(dY=dh, X=w["g"][l], M=d, N=f, K=M, lda=d, ldb=f, part=w["partial_w"],
+            wg = [dict(dY=dy2, X=w["g"][l], M=d, N=f, K=M, lda=d, ldb=f, part=w["partial_w"],
                        c_off=o(pl + "feed_forward.output_dense.weight"), accumulate=lacc,
                        bias_off=o(pl + "feed_forward.output_dense.bias"), cs_off=4 * d + f, sq=sq(l, "fc2"))]
-            ops.gemm(dh, p16, du, M=M, N=f, K=d, lda=d, b_layout=MNMAJOR, ldb=f, ldc=f,
+            ops.gemm(dy2, p16, du, M=M, N=f, K=d, lda=d, b_layout=MNMAJOR, ldb=f, ldc=f,
                      b_off=o(pl + "feed_forward.output_dense.weight"), epilogue=EPI_DGELU, R=w["u"][l],
                      ldr=f, dropout_p=drop_p, dropout_seed=self.step_seed * 1000 + l)
             # FFN1
@@ -800,16 +887,17 @@ class Wav2Vec2CTCEngine:
             # (with the side stream, the d gamma | d beta partials of the layer's two norms are reduced there: two
             # tiny dependent launches less per layer on the critical stream)
             lnp = w["ln_partial"][it & 1]
-            ops.layernorm_bwd(other, w["h1"][l], st.view(pl + "final_layer_norm.weight"), None, w["st2"][l],
-                              dh, dh1, None, None, lnp[0], M, d)
-            # out_proj: h1 = h + Wo ctx + bo
-            wg.append(dict(dY=dh1, X=w["ctx"][l], M=d, N=d, K=M, lda=d, ldb=d, part=w["partial_w"],
+            ln_bwd(other, w["h1"][l], pl + "final_layer_norm.weight", w["st2"][l], dh, dh1, dh1m, drop_o, None, None,
+                   lnp[0])
+            # out_proj: h1 = h + dropout(Wo ctx + bo)
+            dy1 = dh1 if dh1m is None else dh1m
+            wg.append(dict(dY=dy1, X=w["ctx"][l], M=d, N=d, K=M, lda=d, ldb=d, part=w["partial_w"],
                            c_off=o(pl + "attention.out_proj.weight"), accumulate=lacc,
                            bias_off=o(pl + "attention.out_proj.bias"), cs_off=3 * d, sq=sq(l, "o")))
             dctx = other
-            ops.gemm(dh1, p16, dctx, M=M, N=d, K=d, lda=d, b_layout=MNMAJOR, ldb=d, ldc=d,
+            ops.gemm(dy1, p16, dctx, M=M, N=d, K=d, lda=d, b_layout=MNMAJOR, ldb=d, ldc=d,
                      b_off=o(pl + "attention.out_proj.weight"))
-            self._attention_bwd(w, l, dctx, B, T, Tp, H, hd, d, scale, dqkv)
+            self._attention_bwd(w, l, dctx, B, T, Tp, H, hd, d, scale, dqkv, self.dropout_site("attention", l, tr))
             wg.append(dict(dY=dqkv, X=w["x1"][l], M=3 * d, N=d, K=M, lda=3 * d, ldb=d, part=w["partial_w"],
                            c_off=o(pl + "attention.q_proj.weight"), accumulate=lacc,
                            bias_off=o(pl + "attention.q_proj.bias"), cs_off=0, sq=sq(l, "qkv")))
@@ -826,9 +914,8 @@ class Wav2Vec2CTCEngine:
             ops.gemm(dqkv, p16, dx1, M=M, N=d, K=3 * d, lda=3 * d, b_layout=MNMAJOR, ldb=d, ldc=d,
                      b_off=o(pl + "attention.q_proj.weight"))
             # LN1: dh_in = dh1 + LN'(dx1)
-            ops.layernorm_bwd(dx1, hin, st.view(pl + "layer_norm.weight"), None, w["st1"][l], dh1, dh_next,
-                              None, None, lnp[1], M, d)
-            dh = dh_next
+            ln_bwd(dx1, hin, pl + "layer_norm.weight", w["st1"][l], dh1, dh_next, dhm_next, drop_n, None, None, lnp[1])
+            dh, dhm = dh_next, dhm_next
 
             # the layer's second stages in ONE launch: the fused bias-gradient partials of the weight-gradient kernels
             # and the d gamma | d beta partials of its two norms (weight and bias gradients of a norm are adjacent in the
@@ -863,7 +950,8 @@ class Wav2Vec2CTCEngine:
         Cg = d // G
         Tpad = T + K
         dpc = w["dC"]
-        ops.dgelu_mul(dh, w["pc_pre"], dpc, M * d)
+        dg = dh if dhm is None else dhm  # (hidden dropout on h0 + pos_conv(h0): both terms see the masked gradient)
+        ops.dgelu_mul(dg, w["pc_pre"], dpc, M * d)
         ops.colsum(dpc, d, M, d, g32, part, out_off=o("wav2vec2.encoder.pos_conv_embed.conv.bias"))
         # weight gradient in GEMM layout [G][Cg][K][Cg], then through the weight norm
         ops.gemm(dpc, w["xg"], w["dwf"], M=Cg, N=K * Cg, K=M, a_layout=MNMAJOR, lda=d, b_layout=MNMAJOR,
@@ -877,12 +965,15 @@ class Wav2Vec2CTCEngine:
         ops.regroup_pad(dpc, w["dxg"], B, T, G, Cg, K // 2)
         dh0 = w["dA"]
         ops.gemm(w["dxg"], self.pc_wb, dh0, M=T, N=Cg, K=K * Cg, lda=Cg, ldb=K * Cg, ldc=d, a_off=Cg,
-                 epilogue=EPI_RESIDUAL, R=dh, ldr=d, batch1=B, batch2=G, sA=(G * Tpad * Cg, Tpad * Cg),
+                 epilogue=EPI_RESIDUAL, R=dg, ldr=d, batch1=B, batch2=G, sA=(G * Tpad * Cg, Tpad * Cg),
                  sB=(0, Cg * K * Cg), sC=(T * d, Cg), sR=(T * d, Cg))
         # SpecAugment / padding backward: masked rows feed masked_spec_embed, then are zeroed
         if sv["tm"] is not None:
             ops.colsum(dh0, d, M, d, g32, part, rowmask=sv["tm"], out_off=o("wav2vec2.masked_spec_embed"))
         ops.mask_frames(dh0, sv["tm"], sv["fm"], self.zero_embed, flen, B, T, d)
+        pf = self.dropout_site("feat_proj", training=tr)
+        if pf[0] > 0:  # (the projection's output was dropped before SpecAugment / padding)
+            ops.dropout(dh0, dh0, M * d, *pf)
         # feature projection
         fp = "wav2vec2.feature_projection."
         C6 = s.conv_dim[6]
@@ -944,7 +1035,7 @@ class Wav2Vec2CTCEngine:
             self._wstream = ops.side_stream(self.device, "wgrad", int(os.environ.get("CA_WGRAD_PRIO", "0")))
         return self._wstream
 
-    def _attention_bwd(self, w, l, dctx, B, T, Tp, H, hd, d, scale, dqkv=None):
+    def _attention_bwd(self, w, l, dctx, B, T, Tp, H, hd, d, scale, dqkv=None, drop=(0.0, 0)):
         dqkv = w["dqkv"] if dqkv is None else dqkv
         if self.fused_attention:
             qkv = w["qkv"][l]
@@ -952,7 +1043,8 @@ class Wav2Vec2CTCEngine:
                          sdob=T * d, lddq=3 * d, lddk=3 * d, lddv=3 * d, sdqb=T * 3 * d, sdkb=T * 3 * d,
                          sdvb=T * 3 * d, dq_off=0, dk_off=d, dv_off=2 * d, B=B, H=H, Tq=T, Tk=T, hd=hd,
                          Tqp=w["Tqp"], scale=scale, ldq=3 * d, ldk=3 * d, ldv=3 * d, ldo=d, sqb=T * 3 * d,
-                         skb=T * 3 * d, svb=T * 3 * d, sob=T * d, q_off=0, k_off=d, v_off=2 * d, klen=w["flen"])
+                         skb=T * 3 * d, svb=T * 3 * d, sob=T * d, q_off=0, k_off=d, v_off=2 * d, klen=w["flen"],
+                         dropout_p=drop[0], dropout_seed=drop[1])
             return
         qkv, P, dP, dS = w["qkv"][l], w["P"][l], w["S"], w["dS"]
         bs = dict(batch1=B, batch2=H)

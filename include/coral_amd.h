@@ -272,6 +272,14 @@ int ca_layernorm_bwd_ex(const void* dy, const void* x, const float* gamma, const
                         float* dbeta, float* partial, int64_t rows, int32_t C, int32_t act,
                         int32_t x_f32, void* stream);
 
+/* ca_layernorm_bwd_ex (act = 0) with a second bf16 output dx_drop = dropout(dx; p, seed): the keep decision of element
+ * (row, col) is taken from (seed, row * C + col) and applied to the bf16-rounded dx, bit for bit what ca_dropout_bf16
+ * makes of dx.  dx_drop must not alias dx.  p in [0, 1). */
+int ca_layernorm_bwd_dropout(const void* dy, const void* x, const float* gamma, const float* beta,
+                             const float* stats, const void* dres, void* dx, void* dx_drop, float p, uint64_t seed,
+                             float* dgamma, float* dbeta, float* partial, int64_t rows, int32_t C, int32_t x_f32,
+                             void* stream);
+
 /* column sums: out[n] (+)= sum_m x[m*ld + n]  (bias gradients). x bf16, out fp32.
  * rowmask uint8 [rows] or NULL: only rows with a non-zero mask byte are summed (gradient of
  * masked_spec_embed).  partial: fp32 workspace of ca_colsum_partial_floats(rows, N) floats. */

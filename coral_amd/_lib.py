@@ -204,8 +204,6 @@ SIGNATURES = {
         [_vp] * 11 + [_i32, _i64, _i32, _i32, _i32, _f32, _vp],
     ),
     "ca_col2im_1d": (C.c_int, [_vp, _vp, _i32, _i64, _i64, _i32, _i32, _i32, _vp]),
-    "ca_softmax_fwd": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i32, _vp]),
-    "ca_softmax_bwd": (C.c_int, [_vp, _vp, _vp, _f32, _i32, _i32, _i32, _i64, _vp]),
     "ca_ctc_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "ca_ctc_loss_fwd_bwd": (
         C.c_int,

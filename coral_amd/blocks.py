@@ -1,13 +1,19 @@
 """Pre-LN transformer sub-blocks (forward with saved activations + hand-written backward) as sequences
-of libcoral_amd kernels.  Used by the Whisper training path; the three block kinds are exactly the
-ones of `WhisperEncoderLayer` / `WhisperDecoderLayer` ($TF/models/whisper/modeling_whisper.py:379-413,
-448-505): residual self-attention, residual cross-attention, residual GELU feed-forward.
+of libcoral_amd kernels, and the backward schedule of a stack of pre-LN encoder layers (encoder_backward).
+The three block kinds are exactly the ones of `WhisperEncoderLayer` / `WhisperDecoderLayer`
+($TF/models/whisper/modeling_whisper.py:379-413, 448-505): residual self-attention, residual cross-attention,
+residual GELU feed-forward.  The Whisper training path builds its encoder and decoder layers from them; the
+wav2vec2 engine its XLS-R encoder layers (the stable-LayerNorm layer, $TF/models/wav2vec2/modeling_wav2vec2.py:
+611-654, is the same pre-LN self-attention + feed-forward pair).
 
 Every block works on flat row-major bf16 activations [B*T, d] and a `ParamStore` (fp32 masters `p32`,
-bf16 compute copies `p16`, fp32 gradients `g32`); weight gradients are accumulated in fp32.
+bf16 compute copies `p16`, fp32 gradients `g32`); weight gradients are accumulated in fp32.  Workspaces come
+from the caller's allocator z(n, dt=torch.bfloat16) (zero-filled).
 """
 
 from __future__ import annotations
+
+import os
 
 import torch
 
@@ -19,21 +25,28 @@ def _z(n, dev, dt=torch.bfloat16):
     return torch.zeros(n, dtype=dt, device=dev)
 
 
-class Scratch:
-    """Shared backward scratch for one (rows, d, f) problem size."""
+def zeros_on(dev):
+    """The allocator of a workspace made of separate zero-filled tensors."""
+    return lambda n, dt=torch.bfloat16: _z(n, dev, dt)
 
-    def __init__(self, M, d, f, dev, Mkv=0):
-        self.dx = _z(M * d, dev)
-        self.dctx = _z(M * d, dev)
-        self.dqkv = _z(M * 3 * d, dev)
-        self.du = _z(M * f, dev)
-        self.dkv = _z(Mkv * 2 * d, dev) if Mkv else None
-        self.dq = _z(M * d, dev) if Mkv else None  # cross-attention dq: lives until the layer's deferred weight gradients
+
+class Scratch:
+    """Shared backward scratch for one (rows, d, f) problem size.  masks=False: no dropout(dh) buffers (the caller
+    hands the blocks their masked gradients, encoder_backward's `mring`)."""
+
+    def __init__(self, M, d, f, z, Mkv=0, masks=True):
+        self.dx = z(M * d)
+        # (a self-attention block's dctx is dead before its dx is written; the cross-attention block needs both)
+        self.dctx = z(M * d) if Mkv else self.dx
+        self.dqkv = z(M * 3 * d)
+        self.du = z(M * f)
+        self.dkv = z(Mkv * 2 * d) if Mkv else None
+        self.dq = z(M * d) if Mkv else None  # cross-attention dq: lives until the layer's deferred weight gradients
         # dropout(dh): the gradient entering a sub-layer whose output was dropped (hidden dropout); one buffer per block
         # kind so that a layer's deferred weight gradients can read both
-        self.dm = {"attn": _z(M * d, dev), "ffn": _z(M * d, dev), "cross": _z(M * d, dev)}
+        self.dm = {"attn": z(M * d), "ffn": z(M * d), "cross": z(M * d)} if masks else None
         npart = max(ops.layernorm_bwd_partial_floats(M, d), ops.colsum_partial_floats(max(M, Mkv), max(f, 3 * d)), 4096)
-        self.part = _z(npart, dev, torch.float32)
+        self.part = z(npart, torch.float32)
 
 
 def _masked_grad(dh, sv, sc: "Scratch", n, kind):
@@ -55,14 +68,25 @@ def _masked_grad_fp8(dh, sv, sc: "Scratch", M, d, kind, fb):
     return sc.dm[kind] if p > 0.0 else dh
 
 
-def _ln_bwd(st, ln, dx, sv, dh, dhin, sc: "Scratch", M, d, ln_part, pending):
-    """The pre-norm's backward: dhin = dh + LN'(dx).  d gamma | d beta (adjacent in the flat buffer) either reduced right
-    away, or left as partials in `ln_part` with the reduction appended to `pending`."""
+def layernorm_bwd(dy, x, gamma, stats, dres, dx, dgamma, dbeta, part, M, d, xdrop=None):
+    """dx = dres + LN'(dy).  xdrop = (p, seed, buf): the same pass also leaves dropout(dx) in buf - the gradient of the
+    sub-layer below when its output went through hidden dropout (ca_layernorm_bwd_dropout)."""
+    if xdrop is None:
+        ops.layernorm_bwd(dy, x, gamma, None, stats, dres, dx, dgamma, dbeta, part, M, d)
+    else:
+        ops.layernorm_bwd_dropout(dy, x, gamma, None, stats, dres, dx, xdrop[2], xdrop[0], xdrop[1], dgamma, dbeta, part,
+                                  M, d)
+
+
+def _ln_bwd(st, ln, dx, sv, dh, dhin, sc: "Scratch", M, d, ln_part, pending, xdrop=None):
+    """The pre-norm's backward: dhin = dh + LN'(dx) (and dropout(dhin), see layernorm_bwd).  d gamma | d beta (adjacent
+    in the flat buffer) either reduced right away, or left as partials in `ln_part` with the reduction appended to
+    `pending`."""
     if pending is None:
-        ops.layernorm_bwd(dx, sv["hin"], st.view(ln + ".weight"), None, sv["st"], dh, dhin,
-                          st.view(ln + ".weight", "g32"), st.view(ln + ".bias", "g32"), sc.part, M, d)
+        layernorm_bwd(dx, sv["hin"], st.view(ln + ".weight"), sv["st"], dh, dhin, st.view(ln + ".weight", "g32"),
+                      st.view(ln + ".bias", "g32"), sc.part, M, d, xdrop)
         return
-    ops.layernorm_bwd(dx, sv["hin"], st.view(ln + ".weight"), None, sv["st"], dh, dhin, None, None, ln_part, M, d)
+    layernorm_bwd(dx, sv["hin"], st.view(ln + ".weight"), sv["st"], dh, dhin, None, None, ln_part, M, d, xdrop)
     pending.append((ln_part, ops.layernorm_bwd_partial_floats(M, d) // (2 * d), 2 * d, 2 * d, st.g32[st.off(ln + ".weight"):], True))
 
 
@@ -76,12 +100,11 @@ class SelfAttnBlock:
         # grouped weight-gradient launch); the encoder layout, a decoder layer sets its own
         self.cs_qkv, self.cs_o = 0, 3 * d
 
-    def alloc(self, B, T, dev):
+    def alloc(self, B, T, z):
         d, H = self.d, self.H
         Tqp = (T + 31) // 32 * 32
-        return dict(x=_z(B * T * d, dev), st=_z(B * T * 2, dev, torch.float32), qkv=_z(B * T * 3 * d, dev),
-                    ctx=_z(B * T * d, dev), lse=_z(B * H * Tqp, dev, torch.float32), Dq=_z(B * H * Tqp, dev, torch.float32),
-                    Tqp=Tqp)
+        return dict(x=z(B * T * d), st=z(B * T * 2, torch.float32), qkv=z(B * T * 3 * d), ctx=z(B * T * d),
+                    lse=z(B * H * Tqp, torch.float32), Dq=z(B * H * Tqp, torch.float32), Tqp=Tqp)
 
     def _akw(self, B, T, sv, klen):
         d, H = self.d, self.H
@@ -124,20 +147,24 @@ class SelfAttnBlock:
                      dropout_p=hdrop[0], dropout_seed=hdrop[1])
         sv["hin"], sv["klen"], sv["hdrop"] = hin, klen, hdrop
 
-    def backward(self, dh, dhin, sv, sc: Scratch, B, T, defer=None, acc=True, sq=None, ln_part=None, pending=None):
+    def backward(self, dh, dhin, sv, sc: Scratch, B, T, defer=None, acc=True, sq=None, ln_part=None, pending=None,
+                 dy=None, xdrop=None, deferred=None):
         """dh: grad wrt h_out (kept intact); dhin: output buffer for grad wrt h_in (may alias nothing of sv).
         ln_part / pending: leave the norm's d gamma | d beta partials in `ln_part` and append their second-stage
         reduction to `pending` (the caller runs a layer's reductions as one launch, ops.reduce_rows_multi).
         defer: list collecting the block's weight-gradient problems instead of launching them (the caller launches
-        the whole layer's group once dh and sc.dqkv are no longer needed elsewhere).  acc=False: the weight gradients
-        overwrite (first micro-batch of a step, matrices not cleared); sq: {"o": (slots, off), "qkv": ...} where the
-        weight-gradient GEMMs leave their per-tile sums of squares (CaGemmDesc.c_sumsq)."""
+        the whole layer's group once dh and sc.dqkv are no longer needed elsewhere); deferred(): called as soon as
+        they are in the list, before the q|k|v data gradient.  acc=False: the weight gradients overwrite (first
+        micro-batch of a step, matrices not cleared); sq: {"o": (slots, off), "qkv": ...} where the weight-gradient GEMMs
+        leave their per-tile sums of squares (CaGemmDesc.c_sumsq).  dy: the gradient wrt the output before hidden
+        dropout, computed by the caller (default: dropout(dh) here); xdrop: see layernorm_bwd."""
         sq = sq or {}
         st, d = self.st, self.d
         M = B * T
         o, g32, p16 = st.off, st.g32, st.p16
         fb = getattr(self, "fp8_bwd", None) if getattr(self, "fp8", None) is not None else None
-        dy = _masked_grad(dh, sv, sc, M * d, "attn") if fb is None else _masked_grad_fp8(dh, sv, sc, M, d, "attn", fb)
+        if dy is None:
+            dy = _masked_grad(dh, sv, sc, M * d, "attn") if fb is None else _masked_grad_fp8(dh, sv, sc, M, d, "attn", fb)
         # with `defer` the bias gradients travel with the problems (fused into the grouped launch or done by it)
         if defer is None:
             ops.colsum(dy, d, M, d, g32, sc.part, out_off=o(self.attn + "out_proj.bias"))
@@ -159,10 +186,12 @@ class SelfAttnBlock:
                        **(dict(bias_off=o(self.qbias), part=sc.part, cs_off=self.cs_qkv) if defer is not None else {})))
         if defer is not None:
             defer.extend(wg)
+            if deferred is not None:
+                deferred()
         else:
             ops.wgrad_gemm_group(wg, g32)  # both weight gradients of the block in one grouped launch
         ops.gemm(dqkv, p16, sc.dx, M=M, N=d, K=3 * d, lda=3 * d, b_layout=MNMAJOR, ldb=d, ldc=d, b_off=o(self.attn + "q_proj.weight"))
-        _ln_bwd(st, self.ln, sc.dx, sv, dh, dhin, sc, M, d, ln_part, pending)
+        _ln_bwd(st, self.ln, sc.dx, sv, dh, dhin, sc, M, d, ln_part, pending, xdrop)
 
 
 class CrossAttnBlock:
@@ -251,8 +280,8 @@ class FFNBlock:
         self.st, self.ln, self.fc1, self.fc2, self.d, self.f, self.eps = store, ln, fc1, fc2, d, f, eps
         self.cs_fc1, self.cs_fc2 = 4 * d, 4 * d + f  # (the encoder layer's bias vector; see SelfAttnBlock)
 
-    def alloc(self, M, dev):
-        return dict(x=_z(M * self.d, dev), st=_z(M * 2, dev, torch.float32), u=_z(M * self.f, dev), g=_z(M * self.f, dev))
+    def alloc(self, M, z):
+        return dict(x=z(M * self.d), st=z(M * 2, torch.float32), u=z(M * self.f), g=z(M * self.f))
 
     def forward(self, hin, hout, sv, M, dropout_p=0.0, seed=0, hdrop=(0.0, 0)):
         st, d, f = self.st, self.d, self.f
@@ -282,13 +311,16 @@ class FFNBlock:
                      dropout_seed=hdrop[1])
         sv["hin"], sv["drop"], sv["hdrop"] = hin, (dropout_p, seed), hdrop
 
-    def backward(self, dh, dhin, sv, sc: Scratch, M, defer=None, acc=True, sq=None, ln_part=None, pending=None):
+    def backward(self, dh, dhin, sv, sc: Scratch, M, defer=None, acc=True, sq=None, ln_part=None, pending=None, dy=None,
+                 xdrop=None):
+        """(SelfAttnBlock.backward)"""
         sq = sq or {}
         st, d, f = self.st, self.d, self.f
         o, g32, p16 = st.off, st.g32, st.p16
         p, seed = sv["drop"]
         fb = getattr(self, "fp8_bwd", None) if getattr(self, "fp8", None) is not None else None
-        dy = _masked_grad(dh, sv, sc, M * d, "ffn") if fb is None else _masked_grad_fp8(dh, sv, sc, M, d, "ffn", fb)
+        if dy is None:
+            dy = _masked_grad(dh, sv, sc, M * d, "ffn") if fb is None else _masked_grad_fp8(dh, sv, sc, M, d, "ffn", fb)
         if defer is None:
             ops.colsum(dy, d, M, d, g32, sc.part, out_off=o(self.fc2 + ".bias"))
         wg = [dict(dY=dy, X=sv["g"], M=d, N=f, K=M, lda=d, ldb=f, c_off=o(self.fc2 + ".weight"), accumulate=acc,
@@ -319,4 +351,123 @@ class FFNBlock:
                          b_off=du8["w_off"])
         else:
             ops.gemm(sc.du, p16, sc.dx, M=M, N=d, K=f, lda=f, b_layout=MNMAJOR, ldb=d, ldc=d, b_off=o(self.fc1 + ".weight"))
-        _ln_bwd(st, self.ln, sc.dx, sv, dh, dhin, sc, M, d, ln_part, pending)
+        _ln_bwd(st, self.ln, sc.dx, sv, dh, dhin, sc, M, d, ln_part, pending, xdrop)
+
+
+def wgrad_stream(engine):
+    """The side stream of an engine's encoder weight gradients (None = everything on the current stream;
+    CA_WGRAD_STREAM=0)."""
+    if os.environ.get("CA_WGRAD_STREAM", "1") == "0":
+        return None
+    if getattr(engine, "_wstream", None) is None:
+        engine._wstream = ops.side_stream(engine.device, "wgrad", int(os.environ.get("CA_WGRAD_PRIO", "0")))
+    return engine._wstream
+
+
+def norm_plan(store, matrices, device):
+    """Squared gradient norm without a pass over the listed weight matrices, (layer, key, name, rows, cols): their
+    weight-gradient GEMMs leave per-tile sums of squares in `slots` at slot_off[(layer, key)] (CaGemmDesc.c_sumsq;
+    encoder_backward passes the slices), everything else of the flat gradient buffer is listed as chunks of <= 64 Ki
+    floats for ca_sumsq_ranges_f32.  None without matrices."""
+    if not matrices:
+        return None
+    off, soff, mats = 0, {}, []
+    for l, key, name, M, N in matrices:
+        soff[(l, key)] = off
+        off += ops.sumsq_slots(M, N)
+        mats.append((store.off(name), M * N))
+    chunks, pos = [], 0
+    for a, n in sorted(mats) + [(store.numel, 0)]:
+        while pos < a:
+            m = min(65536, a - pos)
+            chunks.append((pos, m))
+            pos += m
+        pos = max(pos, a + n)
+    return dict(slots=torch.zeros(off, dtype=torch.float32, device=device), nslots=off, slot_off=soff,
+                chunks=torch.tensor(chunks, dtype=torch.int64, device=device), nchunks=len(chunks),
+                partial=torch.zeros(max(4096, len(chunks)), dtype=torch.float32, device=device))
+
+
+def encoder_backward(blocks, svs, keep, B, T, ring, scs, bias_ws, ln_parts, *, gm, acc, plan, names, side, wgrad_early,
+                     matrix_range, done, below=None, mring=None, epilogue=None):
+    """Backward through a stack of pre-LN encoder layers, blocks[l] = (SelfAttnBlock, FFNBlock) with saved states
+    svs[l], from the gradient wrt the stack's output in ring[0] down to the one wrt its input.
+
+    A layer's four weight gradients go out as one grouped launch into `gm` (g32, or the bf16 g16; fused bias column sums
+    into g32), its second stages (both norms' d gamma | d beta, the bias vector) as one reduce_rows_multi.  With a `side`
+    stream both run there beside the next layers' data-gradient chain: what they read rotates through the six buffers
+    `ring` (layer i: 2i, 2i+1, 2i+2 mod 6) and two sets of `scs` / `bias_ws` / `ln_parts`, and the main stream waits for
+    layer i's side work before layer i + 2 reuses them.  wgrad_early: the grouped launch goes out right after the
+    attention backward (its second stage at the end of the layer), else both at the end.  epilogue(l) runs behind the
+    second stage, then done(names[l]) - with the side stream current.  acc=False: the matrices' gradients are
+    overwritten, and those of a dropped layer (keep[l] False, matrix_range(l) = (lo, hi)) cleared with its norm slots.
+
+    below(l) -> (p, seed): the hidden dropout on the output of the sub-layer below layer l (dropped layers skipped).
+    With it the LayerNorm backwards also write the dropped gradients of the sub-layers below into `mring` (parallel to
+    `ring`; the caller writes mring[0]) and the blocks read them from there; without it each block masks its own.
+    Returns (the gradient wrt the stack's input, its masked copy or None, a free ring buffer)."""
+    main = torch.cuda.current_stream()
+
+    def on_side(fn):
+        """Run fn on the side stream once the main stream has passed this point (in line without a side stream)."""
+        if side is None:
+            return fn()
+        ev = torch.cuda.Event()
+        ev.record(main)
+        side.wait_event(ev)
+        with torch.cuda.stream(side):
+            return fn()
+
+    wdone, it = {}, 0
+    for l in reversed(range(len(blocks))):
+        if not keep[l]:
+            if not acc:  # dropped layer: its (uncleared) matrices get no gradient this step
+                lo, hi = matrix_range(l)
+                ops.clear_ranges(gm, ((lo, hi - lo),))
+                if plan is not None:
+                    a0 = plan["slot_off"][(l, "qkv")]
+                    ops.clear_f32(plan["slots"], plan["slot_off"].get((l + 1, "qkv"), plan["nslots"]) - a0, off=a0)
+            done(names[l])
+            continue
+        sa, ff = blocks[l]
+        sv_a, sv_f = svs[l]
+        st, g32 = sa.st, sa.st.g32
+        nb = 5 * sa.d + ff.f  # the layer's bias vector: q|k|v, out_proj, fc1, fc2
+        if side is not None and it - 2 in wdone:
+            main.wait_event(wdone.pop(it - 2))
+        sc, bw, lnp = scs[it & 1], bias_ws[it & 1], ln_parts[it & 1]
+        i0, i1, i2 = (2 * it) % 6, (2 * it + 1) % 6, (2 * it + 2) % 6
+        sq = {k: (plan["slots"], plan["slot_off"][(l, k)]) for k in ("qkv", "o", "fc1", "fc2")} if plan is not None else None
+        kw_f = kw_a = {}
+        if below is not None:
+            pa, pb = sv_a["hdrop"], below(l)
+            kw_f = dict(dy=mring[i0] if sv_f["hdrop"][0] > 0 else ring[i0], xdrop=(*pa, mring[i1]) if pa[0] > 0 else None)
+            kw_a = dict(dy=mring[i1] if pa[0] > 0 else ring[i1], xdrop=(*pb, mring[i2]) if pb[0] > 0 else None)
+        wg, second, fused = [], [], [False]
+
+        def wgrads():
+            fused[0] = ops.wgrad_gemm_group(wg, gm, colsum_ws=bw, colsum_ld=nb, Gb=g32)
+
+        ff.backward(ring[i0], ring[i1], sv_f, sc, B * T, defer=wg, acc=acc, sq=sq, ln_part=lnp[0], pending=second, **kw_f)
+        sa.backward(ring[i1], ring[i2], sv_a, sc, B, T, defer=wg, acc=acc, sq=sq, ln_part=lnp[1], pending=second,
+                    deferred=(lambda: on_side(wgrads)) if wgrad_early else None, **kw_a)
+
+        def finish():
+            if not wgrad_early:
+                wgrads()
+            if fused[0]:
+                second.append((bw, ops.COLSUM_PARTS, nb, nb, g32[st.off(sa.qbias):], True))
+            ops.reduce_rows_multi(second)
+            if epilogue is not None:
+                epilogue(l)
+            if side is not None:
+                wdone[it] = torch.cuda.Event()
+                wdone[it].record(side)
+            done(names[l])
+
+        on_side(finish)
+        it += 1
+    if side is not None:
+        main.wait_stream(side)
+    k = (2 * it) % 6
+    return ring[k], (mring[k] if mring is not None else None), ring[(k + 1) % 6]

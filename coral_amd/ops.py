@@ -516,16 +516,6 @@ def col2im_1d(dcol, dx, B, T, L, Cn, k, stride):
     check(lib().ca_col2im_1d(_p(dcol), _p(dx), B, T, L, Cn, k, stride, _stream()), "ca_col2im_1d")
 
 
-def softmax_fwd(scores, probs, klen, BH, H, Tq, Tk, ld, causal=False):
-    check(lib().ca_softmax_fwd(_p(scores), _p(probs), _p(klen), BH, H, Tq, Tk, ld, int(causal),
-                               _stream()), "ca_softmax_fwd")
-
-
-def softmax_bwd(dprobs, probs, dscores, scale, BH, Tq, Tk, ld):
-    check(lib().ca_softmax_bwd(_p(dprobs), _p(probs), _p(dscores), scale, BH, Tq, Tk, ld,
-                               _stream()), "ca_softmax_bwd")
-
-
 def ctc_workspace_bytes(B, T, Lmax):
     return lib().ca_ctc_workspace_bytes(B, T, Lmax)
 

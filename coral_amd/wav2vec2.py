@@ -10,8 +10,8 @@ HBM layout
   * parameters: one flat fp32 master buffer + one flat fp32 gradient buffer + one flat bf16
     compute copy (same offsets), ordered [front | layer 0 | ... | layer L-1 | head] so that a
     data-parallel bucket is a contiguous slice (see coral_amd/trainer.py);
-  * activations: channels-last [B*T, C] bf16; q,k,v of a layer live in one [B*T, 3d] matrix;
-    attention scores/probabilities are [B, H, T, Tp] with Tp = T rounded up to 8;
+  * activations: channels-last [B*T, C] bf16; q,k,v of a layer live in one [B*T, 3d] matrix; the encoder
+    layers are blocks.SelfAttnBlock + blocks.FFNBlock (fused attention, no [T, T] matrix in HBM);
   * conv layers 1..6 and the grouped positional conv run as implicit GEMMs over overlapping-row
     views (no im2col is ever materialised in the forward pass).
 """
@@ -25,8 +25,9 @@ from dataclasses import dataclass
 import torch
 
 from . import ops
+from .blocks import FFNBlock, Scratch, SelfAttnBlock, encoder_backward, layernorm_bwd, norm_plan, wgrad_stream
 from .staging import PinnedStager
-from .ops import EPI_DGELU, EPI_GELU, EPI_GELU_RESIDUAL, EPI_NONE, EPI_RESIDUAL, KMAJOR, MNMAJOR
+from .ops import EPI_GELU_RESIDUAL, EPI_RESIDUAL, MNMAJOR
 
 
 @dataclass
@@ -223,17 +224,13 @@ DROPOUT_SITES = {"attention": (1, "attention_dropout"), "attn_out": (2, "hidden_
 class Wav2Vec2CTCEngine:
     """Forward + backward of Wav2Vec2ForCTC as a fixed sequence of HIP kernels."""
 
-    def __init__(self, shape: Wav2Vec2Shape, device="cuda:0", freeze_base: bool = False,
-                 fused_attention: bool = True):
+    def __init__(self, shape: Wav2Vec2Shape, device="cuda:0", freeze_base: bool = False):
         site_p = [float(getattr(shape, k)) for k in {key for _, key in DROPOUT_SITES.values()}]
         if not all(0.0 <= v < 1.0 for v in site_p):
             raise ValueError(f"dropout probabilities must lie in [0, 1): {shape}")
-        if not fused_attention and shape.attention_dropout > 0:
-            raise ValueError("attention_dropout needs the fused attention kernels (fused_attention=True)")
         if shape.num_hidden_layers > 100 and any(site_p):
             raise ValueError("at most 100 encoder layers with dropout: the seeds of a step give every site a block of 100")
         self.s = shape
-        self.fused_attention = fused_attention  # False: batched-GEMM + softmax kernels (A/B reference)
         self.device = torch.device(device)
         ops.lib()  # fail loudly if the HIP library is not built
         if not torch.cuda.is_available():
@@ -243,6 +240,14 @@ class Wav2Vec2CTCEngine:
         assert s.hidden_size % 8 == 0 and (s.hidden_size // s.num_conv_pos_embedding_groups) % 8 == 0
         assert s.head_dim % 8 == 0
         self.store = ParamStore(w2v2_param_list(s), self.device)
+        self.blocks = []  # encoder layer l: (self-attention block, feed-forward block)
+        for l in range(s.num_hidden_layers):
+            p = f"wav2vec2.encoder.layers.{l}."
+            self.blocks.append((
+                SelfAttnBlock(self.store, p + "layer_norm", p + "attention.", s.num_attention_heads, s.hidden_size,
+                              s.layer_norm_eps, False, p + "attention.q_proj.bias"),
+                FFNBlock(self.store, p + "final_layer_norm", p + "feed_forward.intermediate_dense",
+                         p + "feed_forward.output_dense", s.hidden_size, s.intermediate_size, s.layer_norm_eps)))
         self.freeze_base = freeze_base
         self.training = False
         self._ws = None
@@ -337,34 +342,14 @@ class Wav2Vec2CTCEngine:
                 ("fc2", pl + "feed_forward.output_dense.weight", d, f)]
 
     def norm_plan(self):
-        """Squared gradient norm without a pass over the layer weight matrices (>99 % of the buffer): their
-        weight-gradient GEMMs leave per-tile sums of squares in `slots` (CaGemmDesc.c_sumsq; backward() passes the
-        slices), everything else of the flat buffer is listed as chunks for ca_sumsq_ranges_f32.  None when the model
-        is frozen up to the head (the norm then covers the head bucket only)."""
+        """Squared gradient norm without a pass over the layer weight matrices (>99 % of the buffer; blocks.norm_plan).
+        None when the model is frozen up to the head (the norm then covers the head bucket only)."""
         if self.freeze_base:
             return None
-        if getattr(self, "_norm_plan", None) is not None:
-            return self._norm_plan
-        st, L = self.store, self.s.num_hidden_layers
-        off, soff, mats = 0, {}, []
-        for l in range(L):
-            for key, name, M, N in self._layer_matrices(l):
-                soff[(l, key)] = off
-                off += ops.sumsq_slots(M, N)
-                mats.append((st.off(name), M * N))
-        # complement of the matrices inside [0, numel), cut into chunks of <= 64 Ki floats
-        chunks, pos = [], 0
-        for a, n in sorted(mats) + [(st.numel, 0)]:
-            while pos < a:
-                m = min(65536, a - pos)
-                chunks.append((pos, m))
-                pos += m
-            pos = max(pos, a + n)
-        plan = dict(slots=torch.zeros(off, dtype=torch.float32, device=self.device), nslots=off, slot_off=soff,
-                    chunks=torch.tensor(chunks, dtype=torch.int64, device=self.device), nchunks=len(chunks),
-                    partial=torch.zeros(max(4096, len(chunks)), dtype=torch.float32, device=self.device))
-        self._norm_plan = plan
-        return plan
+        if getattr(self, "_norm_plan", None) is None:
+            self._norm_plan = norm_plan(self.store, [(l, *m) for l in range(self.s.num_hidden_layers)
+                                                     for m in self._layer_matrices(l)], self.device)
+        return self._norm_plan
 
     def shard_ranges(self) -> dict:
         """{layer bucket: (first element of its weight matrices, bucket end)}: the part of every layer bucket a sharded
@@ -471,12 +456,11 @@ class Wav2Vec2CTCEngine:
         if self._ws_key == key:
             return self._ws
         s, dev = self.s, self.device
-        d, f, H = s.hidden_size, s.intermediate_size, s.num_attention_heads
+        d, f = s.hidden_size, s.intermediate_size
         L = s.num_hidden_layers
         Ts = self.conv_lengths(N)
         T = Ts[-1]
         M = B * T
-        Tp = _r8(T)
         G, K = s.num_conv_pos_embedding_groups, s.num_conv_pos_embeddings
         Cg = d // G
         bf, f32 = torch.bfloat16, torch.float32
@@ -484,7 +468,7 @@ class Wav2Vec2CTCEngine:
         def build(z):
             # (run twice: once to measure, once to carve views out of ONE zero-filled arena - a workspace used to
             # be ~450 separate torch.zeros fills)
-            w = {"B": B, "N": N, "Ts": Ts, "T": T, "M": M, "Tp": Tp}
+            w = {"B": B, "N": N, "Ts": Ts, "T": T, "M": M}
             C0 = s.conv_dim[0]
             cdt = f32 if CONV_F32 else bf
             w["a"] = [z(B * Ts[i] * s.conv_dim[i], dt=cdt if i == 6 else bf) for i in range(7)]  # conv block outputs
@@ -496,24 +480,8 @@ class Wav2Vec2CTCEngine:
             w["xg"] = z(B * G * (T + K) * Cg + 8 * Cg)
             w["pc_pre"] = z(M * d)
             w["h"] = [z(M * d) for _ in range(L + 1)]      # residual stream entering layer l (h[L] = out)
-            w["x1"] = [z(M * d) for _ in range(L)]
-            w["st1"] = [z(M * 2, dt=f32) for _ in range(L)]
-            w["qkv"] = [z(M * 3 * d) for _ in range(L)]
-            Tqp = (T + 31) // 32 * 32
-            w["Tqp"] = Tqp
-            if self.fused_attention:
-                w["lse"] = [z(B * H * Tqp, dt=f32) for _ in range(L)]
-                w["Dq"] = z(B * H * Tqp, dt=f32)
-            else:
-                w["P"] = [z(B * H * T * Tp) for _ in range(L)]
-            w["ctx"] = [z(M * d) for _ in range(L)]
-            w["h1"] = [z(M * d) for _ in range(L)]
-            w["x2"] = [z(M * d) for _ in range(L)]
-            w["st2"] = [z(M * 2, dt=f32) for _ in range(L)]
-            w["u"] = [z(M * f) for _ in range(L)]
-            w["g"] = [z(M * f) for _ in range(L)]
-            if not self.fused_attention:
-                w["S"] = z(B * H * T * Tp, dt=f32)         # transient scores / dprobs
+            w["h1"] = [z(M * d) for _ in range(L)]         # ... between layer l's attention and feed-forward blocks
+            w["sv"] = [(sa.alloc(B, T, z), ff.alloc(M, z)) for sa, ff in self.blocks]  # the blocks' saved activations
             w["hf"] = z(M * d)
             w["stf"] = z(M * 2, dt=f32)
             Vp = _r8(s.vocab_size)
@@ -524,28 +492,19 @@ class Wav2Vec2CTCEngine:
             w["nll"] = z(B, dt=f32)
             # backward scratch
             w["dA"] = z(M * d)
-            w["dB"] = z(M * d)
-            w["dC"] = z(M * d)
-            w["dqkv"] = z(M * 3 * d)
-            # second copies of the buffers the weight gradients read (dY operands): with the weight gradients on their own
-            # stream (backward()) a layer's dY must stay intact while the next layer's data gradients are being written
-            w["dBr"] = [w["dB"], z(M * d), z(M * d)]
-            w["dCr"] = [w["dC"], z(M * d)]
-            w["dqkvr"] = [w["dqkv"], z(M * 3 * d)]
-            if s.hidden_dropout > 0:
-                # dropout(dh) of the FFN-output site and dropout(dh1) of the attention-output site (hidden dropout): the
-                # second outputs of the LayerNorm backwards, rotating like dBr / dCr (the weight gradients read them)
-                w["dhmr"] = [z(M * d) for _ in range(3)]
-                w["dh1mr"] = [z(M * d) for _ in range(2)]
-            if not self.fused_attention:
-                w["dS"] = z(B * H * T * Tp)
-            w["du"] = z(M * f)
-            w["dur"] = [w["du"], z(M * f)]
+            # the encoder layers' (blocks.encoder_backward): gradients wrt the residual stream and, with hidden dropout, their
+            # masked copies (the second outputs of the LayerNorm backwards), two sets of layer scratch and of fused
+            # bias-gradient partials - what a layer's weight gradients read on their own stream stays intact for two layers
+            w["ring"] = [z(M * d) for _ in range(6)]
+            w["mring"] = [z(M * d) for _ in range(6)] if s.hidden_dropout > 0 else None
+            w["scs"] = [Scratch(M, d, f, z, masks=False) for _ in range(2)]
+            # (partial column sums of the layer's four dY: rows that a problem with fewer than COLSUM_PARTS tile columns
+            # never writes stay zero)
+            w["bias_ws"] = [z(ops.COLSUM_PARTS * (5 * d + f), dt=f32) for _ in range(2)]
+            # LayerNorm-backward partials (d gamma | d beta per row block) of a layer's two norms, two layers in flight
+            w["ln_partial"] = [[z(ops.layernorm_bwd_partial_floats(M, d), dt=f32) for _ in range(2)] for _ in range(2)]
             w["dxg"] = z(B * G * (T + K) * Cg + 8 * Cg)
             w["dwf"] = z(d * K * Cg, dt=f32)
-            # partial column sums of the layer's four dY (fused bias gradients): rows that a problem with fewer than
-            # COLSUM_PARTS tile columns never writes stay zero
-            w["bias_ws"] = z(ops.COLSUM_PARTS * (5 * d + s.intermediate_size), dt=f32)
             nmax = max(B * Ts[i] * s.conv_kernel[i] * s.conv_dim[i - 1] for i in range(1, 7))
             w["dcol"] = z(nmax)
             w["dconv"] = [z(B * Ts[i] * s.conv_dim[i]) for i in range(7)]   # grads wrt conv block outputs
@@ -557,12 +516,6 @@ class Wav2Vec2CTCEngine:
                 ops.colsum_partial_floats(M, max(f, 3 * d)), ops.colsum_partial_floats(B * Ts[1], 512),
                 ops.conv0_bwd_partial_floats(B, N, C0, s.conv_kernel[0], s.conv_stride[0]), 4096)
             w["partial"] = z(pf, dt=f32)
-            w["partial_w"] = z(pf, dt=f32)  # the weight-gradient stream's own scratch
-            # LayerNorm-backward partials (d gamma | d beta per row block) of a layer's two norms, two layers in flight:
-            # their second-stage reductions run on the weight-gradient stream (backward())
-            w["ln_parts"] = ops.layernorm_bwd_partial_floats(M, d) // (2 * d)
-            w["ln_partial"] = [[z(ops.layernorm_bwd_partial_floats(M, d), dt=f32) for _ in range(2)] for _ in range(2)]
-
             return w
 
         w = _arena_build(build, dev, bf)
@@ -583,9 +536,9 @@ class Wav2Vec2CTCEngine:
         x = self._stager.to_device(input_values, torch.float32, "x")
         B, N = x.shape
         w = self._workspace(B, N)
-        d, f, H, hd = s.hidden_size, s.intermediate_size, s.num_attention_heads, s.head_dim
+        d = s.hidden_size
         L = s.num_hidden_layers
-        Ts, T, M, Tp, Vp = w["Ts"], w["T"], w["M"], w["Tp"], w["Vp"]
+        Ts, T, M, Vp = w["Ts"], w["T"], w["M"], w["Vp"]
         eps = s.layer_norm_eps
         p32, p16 = st.p32, st.p16
         o = st.off
@@ -649,35 +602,16 @@ class Wav2Vec2CTCEngine:
             ops.dropout(w["h"][0], w["h"][0], M * d, *pa)
         # encoder layers
         drop_p = s.activation_dropout if self.training else 0.0
-        scale = hd ** -0.5
-        for l in range(L):
+        for l, (sa, ff) in enumerate(self.blocks):
             hin, hout = w["h"][l], w["h"][l + 1]
             if not keep[l]:
                 hout.copy_(hin)
                 continue
             self._await(f"layer{l}")
-            pl = f"wav2vec2.encoder.layers.{l}."
-            ops.layernorm_fwd(hin, st.view(pl + "layer_norm.weight"), st.view(pl + "layer_norm.bias"),
-                              w["x1"][l], w["st1"][l], M, d, eps)
-            ops.gemm(w["x1"][l], p16, w["qkv"][l], M=M, N=3 * d, K=d, lda=d, ldb=d, ldc=3 * d,
-                     b_off=o(pl + "attention.q_proj.weight"), bias=p32, bias_off=o(pl + "attention.q_proj.bias"))
-            self._attention_fwd(w, l, B, T, Tp, H, hd, d, flen, scale, self.dropout_site("attention", l))
-            pb = self.dropout_site("attn_out", l)
-            ops.gemm(w["ctx"][l], p16, w["h1"][l], M=M, N=d, K=d, lda=d, ldb=d, ldc=d,
-                     b_off=o(pl + "attention.out_proj.weight"), bias=p32,
-                     bias_off=o(pl + "attention.out_proj.bias"), epilogue=EPI_RESIDUAL, R=hin, ldr=d,
-                     dropout_p=pb[0], dropout_seed=pb[1])
-            ops.layernorm_fwd(w["h1"][l], st.view(pl + "final_layer_norm.weight"),
-                              st.view(pl + "final_layer_norm.bias"), w["x2"][l], w["st2"][l], M, d, eps)
-            ops.gemm(w["x2"][l], p16, w["u"][l], C2=w["g"][l], M=M, N=f, K=d, lda=d, ldb=d, ldc=f,
-                     b_off=o(pl + "feed_forward.intermediate_dense.weight"), bias=p32,
-                     bias_off=o(pl + "feed_forward.intermediate_dense.bias"), epilogue=EPI_GELU,
-                     dropout_p=drop_p, dropout_seed=self.step_seed * 1000 + l, stream_out=ops.STREAM_U)
-            pc = self.dropout_site("ffn_out", l)
-            ops.gemm(w["g"][l], p16, hout, M=M, N=d, K=f, lda=f, ldb=f, ldc=d,
-                     b_off=o(pl + "feed_forward.output_dense.weight"), bias=p32,
-                     bias_off=o(pl + "feed_forward.output_dense.bias"), epilogue=EPI_RESIDUAL,
-                     R=w["h1"][l], ldr=d, dropout_p=pc[0], dropout_seed=pc[1])
+            sv_a, sv_f = w["sv"][l]
+            sa.forward(hin, w["h1"][l], sv_a, B, T, klen=flen, hdrop=self.dropout_site("attn_out", l),
+                       adrop=self.dropout_site("attention", l))
+            ff.forward(w["h1"][l], hout, sv_f, M, drop_p, self.step_seed * 1000 + l, hdrop=self.dropout_site("ffn_out", l))
         # final LN + lm_head (fp32 logits, ld = Vp)
         self._await("head")
         for l in range(L):  # dropped layers were not waited for above; the backward reads every layer's weights
@@ -693,7 +627,7 @@ class Wav2Vec2CTCEngine:
                  b_off=o("lm_head.weight"), bias=p32, bias_off=o("lm_head.bias"))
         logits = w["logits"].view(B, T, Vp)[:, :, :V]
         out = CTCOutput(logits=logits, loss=None)
-        self._saved = dict(w=w, x=x, flen=flen, keep=keep, tm=tm, fm=fm, drop_p=drop_p, B=B, N=N,
+        self._saved = dict(w=w, x=x, flen=flen, keep=keep, tm=tm, fm=fm, B=B, N=N,
                            has_loss=False, training=self.training)
         if labels is not None:
             lab = self._stager.to_device(labels, torch.int32, "lab")
@@ -715,21 +649,6 @@ class Wav2Vec2CTCEngine:
             self._saved["has_loss"] = True
         return out
 
-    def _attention_fwd(self, w, l, B, T, Tp, H, hd, d, flen, scale, drop=(0.0, 0)):
-        if self.fused_attention:
-            qkv = w["qkv"][l]
-            ops.attn_fwd(qkv, qkv, qkv, w["ctx"][l], w["lse"][l], B=B, H=H, Tq=T, Tk=T, hd=hd, Tqp=w["Tqp"],
-                         scale=scale, ldq=3 * d, ldk=3 * d, ldv=3 * d, ldo=d, sqb=T * 3 * d, skb=T * 3 * d,
-                         svb=T * 3 * d, sob=T * d, q_off=0, k_off=d, v_off=2 * d, klen=flen, dropout_p=drop[0],
-                         dropout_seed=drop[1])
-            return
-        qkv, S, P, ctx = w["qkv"][l], w["S"], w["P"][l], w["ctx"][l]
-        ops.gemm(qkv, qkv, S, M=T, N=T, K=hd, lda=3 * d, ldb=3 * d, ldc=Tp, b_off=d, alpha=scale,
-                 batch1=B, batch2=H, sA=(T * 3 * d, hd), sB=(T * 3 * d, hd), sC=(H * T * Tp, T * Tp))
-        ops.softmax_fwd(S, P, flen, B * H, H, T, T, Tp)
-        ops.gemm(P, qkv, ctx, M=T, N=hd, K=T, lda=Tp, b_layout=MNMAJOR, ldb=3 * d, b_off=2 * d, ldc=d,
-                 batch1=B, batch2=H, sA=(H * T * Tp, T * Tp), sB=(T * 3 * d, hd), sC=(T * d, hd))
-
     # ---- backward ------------------------------------------------------------------------------
     def backward(self, loss_scale: float = 1.0, overwrite_matrices: bool = False, bucket_done=None):
         """Back-propagate d(loss*loss_scale) into the flat gradient buffer (+=).
@@ -744,11 +663,11 @@ class Wav2Vec2CTCEngine:
         s, st = self.s, self.store
         w, x, flen, keep = sv["w"], sv["x"], sv["flen"], sv["keep"]
         B, N = sv["B"], sv["N"]
-        d, f, H, hd = s.hidden_size, s.intermediate_size, s.num_attention_heads, s.head_dim
+        d = s.hidden_size
         L = s.num_hidden_layers
-        Ts, T, M, Tp, Vp = w["Ts"], w["T"], w["M"], w["Tp"], w["Vp"]
+        Ts, T, M, Vp = w["Ts"], w["T"], w["M"], w["Vp"]
         V = s.vocab_size
-        p32, p16, g32 = st.p32, st.p16, st.g32
+        p16, g32 = st.p16, st.g32
         o = st.off
         part = w["partial"]
         acc = True  # small tensors, front and head always accumulate (zero_grad clears them)
@@ -787,170 +706,28 @@ class Wav2Vec2CTCEngine:
             below = [k for k in range(j) if keep[k]]
             return self.dropout_site("ffn_out", below[-1], tr) if below else self.dropout_site("pos_conv", training=tr)
 
-        def ln_bwd(dy, x, ln, stats, dres, dx, dxm, drop, dgamma, dbeta, lpart):
-            """LayerNorm backward; with drop[0] > 0 it also leaves dropout(dx) in dxm (ca_layernorm_bwd_dropout)."""
-            if drop[0] > 0:
-                ops.layernorm_bwd_dropout(dy, x, st.view(ln), None, stats, dres, dx, dxm, drop[0], drop[1], dgamma, dbeta,
-                                          lpart, M, d)
-            else:
-                ops.layernorm_bwd(dy, x, st.view(ln), None, stats, dres, dx, dgamma, dbeta, lpart, M, d)
-
-        dh = w["dB"]
-        # dhm: dropout(dh) with the mask of the hidden-dropout site whose output dh is the gradient of (None: no such
-        # dropout); the gradient of that site's branch, while dh itself carries on down the residual stream
+        ring, mring = w["ring"], w["mring"]
+        # ring[0]: the gradient wrt the residual stream leaving layer L-1; mring[0]: dropout(ring[0]) with the mask of the
+        # hidden-dropout site whose output that stream carries - the gradient of that site's branch
         drop = branch_site(L)
-        dhm = w["dhmr"][0] if drop[0] > 0 else None
-        ln_bwd(w["dA"], w["h"][L], "wav2vec2.encoder.layer_norm.weight", w["stf"], None, dh, dhm, drop,
-               st.view("wav2vec2.encoder.layer_norm.weight", "g32"), st.view("wav2vec2.encoder.layer_norm.bias", "g32"),
-               part)
+        layernorm_bwd(w["dA"], w["h"][L], st.view("wav2vec2.encoder.layer_norm.weight"), w["stf"], None, ring[0],
+                      st.view("wav2vec2.encoder.layer_norm.weight", "g32"), st.view("wav2vec2.encoder.layer_norm.bias", "g32"),
+                      part, M, d, (*drop, mring[0]) if drop[0] > 0 else None)
         done("head")
-        # dh = gradient wrt residual stream leaving layer L-1
-        other = w["dA"]
-        scale = hd ** -0.5
-        drop_p = sv["drop_p"]
-        # Weight gradients on their own stream: dW = dY^T X feeds only the optimiser, so a layer's three weight-gradient
-        # launches (MFMA-bound, 256x256 tiles, one workgroup per CU) run beside the NEXT layer's data-gradient chain
-        # (128x128-tile GEMMs, attention backward, LayerNorm backward: VALU / HBM-bound kernels and GEMM tails that
-        # leave matrix pipes idle).  The dY operands rotate through two (three for dh) buffers; the main stream waits
-        # for the weight gradients of layer i before layer i+2 reuses their buffers.
-        ws = self._wgrad_stream()
-        main = torch.cuda.current_stream()
-        wdone = {}
-        it = 0
-        nb = 5 * d + f  # q|k|v, out, ffn1, ffn2 biases: contiguous in the flat buffer (w2v2_param_list)
-
-        def on_side(ready_event, fn):
-            """Run fn on the weight-gradient stream once `ready_event` (main stream) has passed."""
-            if ws is None:
-                fn()
-                return
-            ws.wait_event(ready_event)
-            with torch.cuda.stream(ws):
-                fn()
-
-        def mark():
-            if ws is None:
-                return None
-            ev = torch.cuda.Event()
-            ev.record(main)
-            return ev
-
-        plan = self.norm_plan()
-
-        def sq(l, key):  # where the weight-gradient GEMM of matrix `key` leaves its per-tile sums of squares
-            return (plan["slots"], plan["slot_off"][(l, key)]) if plan is not None else None
-
-        for l in reversed(range(L)):
-            if not keep[l]:
-                if overwrite_matrices:  # dropped layer: its matrices get no gradient this step
-                    lo = o(f"wav2vec2.encoder.layers.{l}.attention.q_proj.weight")
-                    if self.matrix_grads_bf16:
-                        gm[lo:st.buckets[f"layer{l}"][1]].zero_()
-                    else:
-                        ops.clear_f32(g32, st.buckets[f"layer{l}"][1] - lo, off=lo)
-                    if plan is not None:
-                        a0 = plan["slot_off"][(l, "qkv")]
-                        a1 = plan["slot_off"][(l + 1, "qkv")] if l + 1 < L else plan["nslots"]
-                        ops.clear_f32(plan["slots"], a1 - a0, off=a0)
-                done(f"layer{l}")
-                continue
-            pl = f"wav2vec2.encoder.layers.{l}."
-            hin = w["h"][l]
-            if ws is not None:
-                if it - 2 in wdone:
-                    main.wait_event(wdone.pop(it - 2))
-                dh_next, du, dh1, dqkv = w["dBr"][(it + 1) % 3], w["dur"][it & 1], w["dCr"][it & 1], w["dqkvr"][it & 1]
-                mi, m1 = (it + 1) % 3, it & 1
-            else:
-                dh_next, du, dh1, dqkv = dh, w["du"], w["dC"], w["dqkv"]
-                mi, m1 = 0, 0
-            drop_o, drop_n = self.dropout_site("attn_out", l, tr), branch_site(l)
-            dh1m = w["dh1mr"][m1] if drop_o[0] > 0 else None
-            dhm_next = w["dhmr"][mi] if drop_n[0] > 0 else None
-            dy2 = dh if dhm is None else dhm  # gradient of the FFN output (before hidden dropout)
-            # FFN2: h_out = h1 + W2 g + b2
-            # (bias gradients = column sums of the same dY: taken inside the weight-gradient kernel where it runs
-            # on the 256x256 tiles, see ops.wgrad_gemm)
-            wg = [dict(dY=dy2, X=w["g"][l], M=d, N=f, K=M, lda=d, ldb=f, part=w["partial_w"],
-                       c_off=o(pl + "feed_forward.output_dense.weight"), accumulate=lacc,
-                       bias_off=o(pl + "feed_forward.output_dense.bias"), cs_off=4 * d + f, sq=sq(l, "fc2"))]
-            ops.gemm(dy2, p16, du, M=M, N=f, K=d, lda=d, b_layout=MNMAJOR, ldb=f, ldc=f,
-                     b_off=o(pl + "feed_forward.output_dense.weight"), epilogue=EPI_DGELU, R=w["u"][l],
-                     ldr=f, dropout_p=drop_p, dropout_seed=self.step_seed * 1000 + l)
-            # FFN1
-            wg.append(dict(dY=du, X=w["x2"][l], M=f, N=d, K=M, lda=f, ldb=d, part=w["partial_w"],
-                           c_off=o(pl + "feed_forward.intermediate_dense.weight"), accumulate=lacc,
-                           bias_off=o(pl + "feed_forward.intermediate_dense.bias"), cs_off=4 * d, sq=sq(l, "fc1")))
-            ops.gemm(du, p16, other, M=M, N=d, K=f, lda=f, b_layout=MNMAJOR, ldb=d, ldc=d,
-                     b_off=o(pl + "feed_forward.intermediate_dense.weight"))
-            # LN2: dh1 = dh + LN'(dx2)
-            # (with the side stream, the d gamma | d beta partials of the layer's two norms are reduced there: two
-            # tiny dependent launches less per layer on the critical stream)
-            lnp = w["ln_partial"][it & 1]
-            ln_bwd(other, w["h1"][l], pl + "final_layer_norm.weight", w["st2"][l], dh, dh1, dh1m, drop_o, None, None,
-                   lnp[0])
-            # out_proj: h1 = h + dropout(Wo ctx + bo)
-            dy1 = dh1 if dh1m is None else dh1m
-            wg.append(dict(dY=dy1, X=w["ctx"][l], M=d, N=d, K=M, lda=d, ldb=d, part=w["partial_w"],
-                           c_off=o(pl + "attention.out_proj.weight"), accumulate=lacc,
-                           bias_off=o(pl + "attention.out_proj.bias"), cs_off=3 * d, sq=sq(l, "o")))
-            dctx = other
-            ops.gemm(dy1, p16, dctx, M=M, N=d, K=d, lda=d, b_layout=MNMAJOR, ldb=d, ldc=d,
-                     b_off=o(pl + "attention.out_proj.weight"))
-            self._attention_bwd(w, l, dctx, B, T, Tp, H, hd, d, scale, dqkv, self.dropout_site("attention", l, tr))
-            wg.append(dict(dY=dqkv, X=w["x1"][l], M=3 * d, N=d, K=M, lda=3 * d, ldb=d, part=w["partial_w"],
-                           c_off=o(pl + "attention.q_proj.weight"), accumulate=lacc,
-                           bias_off=o(pl + "attention.q_proj.bias"), cs_off=0, sq=sq(l, "qkv")))
-
-            # the layer's weight gradients (one grouped launch plan: 240 + 240 + 184 + 64 tiles at XLS-R-2B) and the
-            # reduction of their fused bias-gradient partials
-            bias_fused = [False]
-
-            def wgrads(wg=wg, pl=pl, bias_fused=bias_fused):
-                bias_fused[0] = ops.wgrad_gemm_group(wg, gm, colsum_ws=w["bias_ws"], colsum_ld=nb, Gb=g32)
-
-            on_side(mark(), wgrads)
-            dx1 = other
-            ops.gemm(dqkv, p16, dx1, M=M, N=d, K=3 * d, lda=3 * d, b_layout=MNMAJOR, ldb=d, ldc=d,
-                     b_off=o(pl + "attention.q_proj.weight"))
-            # LN1: dh_in = dh1 + LN'(dx1)
-            ln_bwd(dx1, hin, pl + "layer_norm.weight", w["st1"][l], dh1, dh_next, dhm_next, drop_n, None, None, lnp[1])
-            dh, dhm = dh_next, dhm_next
-
-            # the layer's second stages in ONE launch: the fused bias-gradient partials of the weight-gradient kernels
-            # and the d gamma | d beta partials of its two norms (weight and bias gradients of a norm are adjacent in the
-            # flat buffer)
-            def second_stage(pl=pl, lnp=lnp, bias_fused=bias_fused):
-                items = [(lnp[0], w["ln_parts"], 2 * d, 2 * d, g32[o(pl + "final_layer_norm.weight"):], True),
-                         (lnp[1], w["ln_parts"], 2 * d, 2 * d, g32[o(pl + "layer_norm.weight"):], True)]
-                if bias_fused[0]:
-                    items.append((w["bias_ws"], ops.COLSUM_PARTS, nb, nb, g32[o(pl + "attention.q_proj.bias"):], True))
-                ops.reduce_rows_multi(items)
-
-            if ws is None:
-                second_stage()
-                done(f"layer{l}")
-            else:
-                # the bucket is complete once the side stream has passed both its own launches and the main stream's
-                # LayerNorm gradients: the hook runs with the side stream current, so a trainer that makes its
-                # communication / optimiser stream wait for "the current stream" waits for all of the bucket
-                ev = mark()
-                ws.wait_event(ev)
-                with torch.cuda.stream(ws):
-                    second_stage()
-                    wd = torch.cuda.Event()
-                    wd.record(ws)
-                    wdone[it] = wd
-                    done(f"layer{l}")
-            it += 1
-        if ws is not None:
-            main.wait_stream(ws)
+        # Weight gradients on their own stream: dW = dY^T X feeds only the optimiser, so a layer's weight-gradient launch
+        # (MFMA-bound, 256x256 tiles, one workgroup per CU) runs beside the NEXT layer's data-gradient chain (128x128-tile
+        # GEMMs, attention backward, LayerNorm backward: VALU / HBM-bound kernels and GEMM tails that leave matrix pipes
+        # idle); it goes out as soon as the layer's attention backward has produced its last dY.
+        dh, dhm, dpc = encoder_backward(
+            self.blocks, w["sv"], keep, B, T, ring, w["scs"], w["bias_ws"], w["ln_partial"], gm=gm, acc=lacc,
+            plan=self.norm_plan(), names=[f"layer{l}" for l in range(L)], side=wgrad_stream(self), wgrad_early=True,
+            matrix_range=lambda l: self.shard_ranges()[f"layer{l}"], done=done, below=branch_site, mring=mring)
         # dh: gradient wrt h[0] = h0m + gelu(pc_pre)
         G, K = s.num_conv_pos_embedding_groups, s.num_conv_pos_embeddings
         Cg = d // G
         Tpad = T + K
-        dpc = w["dC"]
-        dg = dh if dhm is None else dhm  # (hidden dropout on h0 + pos_conv(h0): both terms see the masked gradient)
+        # (hidden dropout on h0 + pos_conv(h0): both terms see the masked gradient)
+        dg = dhm if branch_site(0)[0] > 0 else dh
         ops.dgelu_mul(dg, w["pc_pre"], dpc, M * d)
         ops.colsum(dpc, d, M, d, g32, part, out_off=o("wav2vec2.encoder.pos_conv_embed.conv.bias"))
         # weight gradient in GEMM layout [G][Cg][K][Cg], then through the weight norm
@@ -1024,42 +801,6 @@ class Wav2Vec2CTCEngine:
                 cache.clear()
             t = cache[v] = torch.full((1,), float(v), dtype=torch.float32, device=self.device)
         return t
-
-    def _wgrad_stream(self):
-        """The weight gradients' stream (None = everything on the current stream; CA_WGRAD_STREAM=0)."""
-        import os
-
-        if os.environ.get("CA_WGRAD_STREAM", "1") == "0":
-            return None
-        if getattr(self, "_wstream", None) is None:
-            self._wstream = ops.side_stream(self.device, "wgrad", int(os.environ.get("CA_WGRAD_PRIO", "0")))
-        return self._wstream
-
-    def _attention_bwd(self, w, l, dctx, B, T, Tp, H, hd, d, scale, dqkv=None, drop=(0.0, 0)):
-        dqkv = w["dqkv"] if dqkv is None else dqkv
-        if self.fused_attention:
-            qkv = w["qkv"][l]
-            ops.attn_bwd(qkv, qkv, qkv, w["ctx"][l], w["lse"][l], dctx, w["Dq"], dqkv, dqkv, dqkv, lddo=d,
-                         sdob=T * d, lddq=3 * d, lddk=3 * d, lddv=3 * d, sdqb=T * 3 * d, sdkb=T * 3 * d,
-                         sdvb=T * 3 * d, dq_off=0, dk_off=d, dv_off=2 * d, B=B, H=H, Tq=T, Tk=T, hd=hd,
-                         Tqp=w["Tqp"], scale=scale, ldq=3 * d, ldk=3 * d, ldv=3 * d, ldo=d, sqb=T * 3 * d,
-                         skb=T * 3 * d, svb=T * 3 * d, sob=T * d, q_off=0, k_off=d, v_off=2 * d, klen=w["flen"],
-                         dropout_p=drop[0], dropout_seed=drop[1])
-            return
-        qkv, P, dP, dS = w["qkv"][l], w["P"][l], w["S"], w["dS"]
-        bs = dict(batch1=B, batch2=H)
-        # dP = dctx V^T
-        ops.gemm(dctx, qkv, dP, M=T, N=T, K=hd, lda=d, ldb=3 * d, b_off=2 * d, ldc=Tp, sA=(T * d, hd),
-                 sB=(T * 3 * d, hd), sC=(H * T * Tp, T * Tp), **bs)
-        ops.softmax_bwd(dP, P, dS, scale, B * H, T, T, Tp)
-        # dQ = dS K ; dK = dS^T Q ; dV = P^T dctx
-        ops.gemm(dS, qkv, dqkv, M=T, N=hd, K=T, lda=Tp, b_layout=MNMAJOR, ldb=3 * d, b_off=d, ldc=3 * d,
-                 c_off=0, sA=(H * T * Tp, T * Tp), sB=(T * 3 * d, hd), sC=(T * 3 * d, hd), **bs)
-        ops.gemm(dS, qkv, dqkv, M=T, N=hd, K=T, a_layout=MNMAJOR, lda=Tp, b_layout=MNMAJOR, ldb=3 * d,
-                 b_off=0, ldc=3 * d, c_off=d, sA=(H * T * Tp, T * Tp), sB=(T * 3 * d, hd),
-                 sC=(T * 3 * d, hd), **bs)
-        ops.gemm(P, dctx, dqkv, M=T, N=hd, K=T, a_layout=MNMAJOR, lda=Tp, b_layout=MNMAJOR, ldb=d, ldc=3 * d,
-                 c_off=2 * d, sA=(H * T * Tp, T * Tp), sB=(T * d, hd), sC=(T * 3 * d, hd), **bs)
 
     # ---- inference helpers -----------------------------------------------------------------------
     def greedy_decode(self, logits_full: torch.Tensor | None = None, in_len=None):

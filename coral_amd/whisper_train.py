@@ -18,7 +18,7 @@ import torch
 
 from . import ops
 from .staging import PinnedStager
-from .blocks import CrossAttnBlock, FFNBlock, Scratch, SelfAttnBlock, _z
+from .blocks import CrossAttnBlock, FFNBlock, Scratch, SelfAttnBlock, _z, encoder_backward, norm_plan, wgrad_stream, zeros_on
 from .ops import EPI_GELU, EPI_GELU_RESIDUAL, MNMAJOR
 from .wav2vec2 import _r8
 from .whisper import WhisperEngine, WhisperShape
@@ -242,30 +242,12 @@ class WhisperTrainEngine(WhisperEngine):
             ops.clear_f32(plan["slots"], plan["nslots"])
 
     def norm_plan(self):
-        """Squared gradient norm without a pass over the encoder layers' weight matrices (wav2vec2.norm_plan)."""
+        """Squared gradient norm without a pass over the encoder layers' weight matrices (blocks.norm_plan)."""
         if self.freeze_base:
             return None
-        if getattr(self, "_norm_plan", None) is not None:
-            return self._norm_plan
-        st = self.store
-        off, soff, mats = 0, {}, []
-        for l in range(self.s.encoder_layers):
-            for key, name, M, N in self._enc_matrices(l):
-                soff[(l, key)] = off
-                off += ops.sumsq_slots(M, N)
-                mats.append((st.off(name), M * N))
-        if not mats:
-            return None
-        chunks, pos = [], 0
-        for a, n in sorted(mats) + [(st.numel, 0)]:
-            while pos < a:
-                m = min(65536, a - pos)
-                chunks.append((pos, m))
-                pos += m
-            pos = max(pos, a + n)
-        self._norm_plan = dict(slots=torch.zeros(off, dtype=torch.float32, device=self.device), nslots=off, slot_off=soff,
-                               chunks=torch.tensor(chunks, dtype=torch.int64, device=self.device), nchunks=len(chunks),
-                               partial=torch.zeros(max(4096, len(chunks)), dtype=torch.float32, device=self.device))
+        if getattr(self, "_norm_plan", None) is None:
+            self._norm_plan = norm_plan(self.store, [(l, *m) for l in range(self.s.encoder_layers)
+                                                     for m in self._enc_matrices(l)], self.device)
         return self._norm_plan
 
     def train(self, mode: bool = True):
@@ -305,22 +287,23 @@ class WhisperTrainEngine(WhisperEngine):
         Tin = 2 * T
         Me, Md = B * T, B * L
         f32 = torch.float32
+        z = zeros_on(dev)
         w = dict(
             xin=_z(B * (Tin + 2) * s.num_mel_bins + 64, dev), pre1=_z(B * (Tin + 2) * d + 64, dev),
             c1=_z(B * (Tin + 2) * d + 64, dev), pre2=_z(Me * d, dev),
             eh=[_z(Me * d, dev) for _ in range(2 * s.encoder_layers + 1)], enc_out=_z(Me * d, dev),
             enc_st=_z(Me * 2, dev, f32),
-            enc_sv=[(sa.alloc(B, T, dev), ff.alloc(Me, dev)) for sa, ff in self.enc_blocks],
+            enc_sv=[(sa.alloc(B, T, z), ff.alloc(Me, z)) for sa, ff in self.enc_blocks],
             dh=[_z(Md * d, dev) for _ in range(3 * s.decoder_layers + 1)], dec_out=_z(Md * d, dev),
             dec_st=_z(Md * 2, dev, f32),
-            dec_sv=[(sa.alloc(B, L, dev), ca.alloc(B, L, T, dev), ff.alloc(Md, dev)) for sa, ca, ff in self.dec_blocks],
+            dec_sv=[(sa.alloc(B, L, z), ca.alloc(B, L, T, dev), ff.alloc(Md, z)) for sa, ca, ff in self.dec_blocks],
             logits=_z(Md * _r8(s.vocab_size), dev, f32), dlogits=_z(Md * _r8(s.vocab_size), dev, f32),
             dlogits16=_z(Md * _r8(s.vocab_size), dev),
             loss_cnt=_z(2, dev, f32),  # loss_sum (fp32) | count (int32) in adjacent words: cleared by one launch
-            sc_e=Scratch(Me, d, s.encoder_ffn_dim, dev), sc_d=Scratch(Md, d, s.decoder_ffn_dim, dev, Mkv=Me),
+            sc_e=Scratch(Me, d, s.encoder_ffn_dim, z), sc_d=Scratch(Md, d, s.decoder_ffn_dim, z, Mkv=Me),
             # (second scratch / bias workspace and three more gradient buffers: the encoder layers' weight gradients run
             # on a side stream two layers behind the data-gradient chain, see backward())
-            sc_e2=Scratch(Me, d, s.encoder_ffn_dim, dev),
+            sc_e2=Scratch(Me, d, s.encoder_ffn_dim, z),
             g_e=[_z(Me * d, dev) for _ in range(6)], g_d=[_z(Md * d, dev) for _ in range(4)], dec_bias_ws=_z(ops.COLSUM_PARTS * (9 * d + s.decoder_ffn_dim), dev, f32),
             # d gamma | d beta partials of a layer's norms until the layer's one second-stage launch (encoder: two sets, its
             # weight-gradient stream runs a layer behind)
@@ -539,11 +522,9 @@ class WhisperTrainEngine(WhisperEngine):
         ops.layernorm_bwd(ea, w["eh"][-1], st.view("model.encoder.layer_norm.weight"), None, w["enc_st"], None, ring[0],
                           st.view("model.encoder.layer_norm.weight", "g32"), st.view("model.encoder.layer_norm.bias", "g32"),
                           sc_e.part, Me, d)
-        # Encoder layers.  Both blocks' dY stay alive until the layer's four weight gradients go out as one grouped
-        # launch (192 tiles of the 256x256 kernel at d = 1024 instead of four split-K launches) - on a side stream beside
-        # the next layers' data-gradient chain (as in the wav2vec2 engine; CA_WGRAD_STREAM=0: in line): layer i works in
-        # ring buffers 2i, 2i+1, 2i+2 (mod 6) and scratch i & 1, so what a layer's weight gradients read is first
-        # overwritten two layers later, behind an event.
+        # Encoder layers (blocks.encoder_backward).  A layer's four weight gradients go out as one grouped launch at the end
+        # of the layer (192 tiles of the 256x256 kernel at d = 1024 instead of four split-K launches), on a side stream
+        # beside the next layers' data-gradient chain (CA_WGRAD_STREAM=0: in line).
         # (measured, interleaved on one box: whisper-large-turbo 89.5 -> 88.3 ms with the side stream, whisper-medium
         # 72.9 -> 73.9 without the rule below: at 12 000 rows the data-gradient GEMMs fill the chip by themselves, and a
         # layer's weight-gradient group that does not - 192 tiles of 256 x 256 at d = 1024 against 300 at d = 1280 - only
@@ -551,63 +532,16 @@ class WhisperTrainEngine(WhisperEngine):
         xt = lambda m, n: ((m + 255) // 256) * ((n + 255) // 256)  # noqa: E731
         fe = s.encoder_ffn_dim
         group_tiles = xt(3 * d, d) + xt(d, d) + xt(fe, d) + xt(d, fe)
-        wside = self._wgrad_stream() if group_tiles >= 256 else None
-        main = torch.cuda.current_stream()
-        scs, bws = (sc_e, w["sc_e2"]), (w["bias_ws"], w["bias_ws2"])
-        wdone, it = {}, 0
-        cur = ring[0]
         plan = self.norm_plan()
-        eacc = not overwrite_matrices  # encoder weight matrices: accumulate, or overwrite in a step's first micro-batch
-        # ... and then, when the trainer asked for it, kept in bf16 - the dtype the reference's autocast computes them in
-        # (wav2vec2.py backward; NOTEBOOK R5.10)
+        # encoder weight matrices: accumulate, or overwrite in a step's first micro-batch and then, when the trainer asked
+        # for it, keep in bf16 - the dtype the reference's autocast computes them in (wav2vec2.py backward; NOTEBOOK R5.10)
         self.matrix_grads_bf16 = bool(overwrite_matrices and getattr(self, "wgrad_bf16", False) and plan is not None)
-        gm = st.g16 if self.matrix_grads_bf16 else g32
-        for l in reversed(range(s.encoder_layers)):
-            sqd = ({k: (plan["slots"], plan["slot_off"][(l, k)]) for k in ("qkv", "o", "fc1", "fc2")}
-                   if plan is not None else None)
-            if not sv["ek"][l]:
-                if overwrite_matrices:  # dropped layer: its (uncleared) matrices get no gradient this step
-                    lo, hi = self._enc_matrix_range(l)
-                    gm[lo:hi].zero_()
-                done(f"enc{l}")
-                continue
-            sa, ff = self.enc_blocks[l]
-            sv_a, sv_f = w["enc_sv"][l]
-            if wside is not None and it - 2 in wdone:
-                main.wait_event(wdone.pop(it - 2))
-            sc, bw = scs[it & 1], bws[it & 1]
-            cur, other, third = ring[(2 * it) % 6], ring[(2 * it + 1) % 6], ring[(2 * it + 2) % 6]
-            wg, second = [], []
-            lpe = w["ln_part_e"][it & 1]
-            ff.backward(cur, other, sv_f, sc, Me, defer=wg, acc=eacc, sq=sqd, ln_part=lpe[0], pending=second)
-            sa.backward(other, third, sv_a, sc, B, T, defer=wg, acc=eacc, sq=sqd, ln_part=lpe[1], pending=second)
-            nb = 5 * d + s.encoder_ffn_dim
-
-            def wgrads(wg=wg, bw=bw, l=l, second=second):
-                if ops.wgrad_gemm_group(wg, gm, colsum_ws=bw, colsum_ld=nb, Gb=g32):
-                    second.append((bw, ops.COLSUM_PARTS, nb, nb,
-                                   g32[o(f"model.encoder.layers.{l}.self_attn.q_proj.bias"):], True))
-                ops.reduce_rows_multi(second)  # both norms' d gamma | d beta and the bias vector: one launch
-                self.clear_internal_grads_of(f"model.encoder.layers.{l}.")
-
-            if wside is None:
-                wgrads()
-                done(f"enc{l}")
-            else:
-                ev = torch.cuda.Event()
-                ev.record(main)
-                wside.wait_event(ev)
-                with torch.cuda.stream(wside):
-                    wgrads()
-                    wd = torch.cuda.Event()
-                    wd.record(wside)
-                    wdone[it] = wd
-                    done(f"enc{l}")  # (hook runs with the side stream current: the bucket is complete behind it)
-            cur = third
-            it += 1
-        if wside is not None:
-            main.wait_stream(wside)
-        other = ring[(2 * it + 1) % 6]
+        cur, _, other = encoder_backward(
+            self.enc_blocks, w["enc_sv"], sv["ek"], B, T, ring, (sc_e, w["sc_e2"]), (w["bias_ws"], w["bias_ws2"]),
+            w["ln_part_e"], gm=st.g16 if self.matrix_grads_bf16 else g32, acc=not overwrite_matrices, plan=plan,
+            names=[f"enc{l}" for l in range(s.encoder_layers)], side=wgrad_stream(self) if group_tiles >= 256 else None,
+            wgrad_early=False, matrix_range=self._enc_matrix_range, done=done,
+            epilogue=lambda l: self.clear_internal_grads_of(f"model.encoder.layers.{l}."))
         done("encf")
         # conv2: h0 = dropout(gelu(pre2) + pos)
         if ep > 0.0:
@@ -633,16 +567,6 @@ class WhisperTrainEngine(WhisperEngine):
         ops.reduce_rows(w["dwr_part"], B, d * 3 * mels, d * 3 * mels, w["dwr"])
         ops.conv_weight_grad_reorder(w["dwr"], g32, d, mels, 3, dw_off=o("model.encoder.conv1.weight"))
         done("front")
-
-    def _wgrad_stream(self):
-        """The encoder weight gradients' stream (None = everything on the current stream; CA_WGRAD_STREAM=0)."""
-        import os
-
-        if os.environ.get("CA_WGRAD_STREAM", "1") == "0":
-            return None
-        if getattr(self, "_wstream", None) is None:
-            self._wstream = ops.side_stream(self.device, "wgrad", int(os.environ.get("CA_WGRAD_PRIO", "0")))
-        return self._wstream
 
     def clear_internal_grads_of(self, prefix: str):
         """The `__zero` slots of one layer, as one launch over a cached range table (called per layer in the backward,

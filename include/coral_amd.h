@@ -375,19 +375,6 @@ int ca_col2im_1d(const void* dcol, void* dx, int32_t B, int64_t T, int64_t L, in
                  int32_t k, int32_t stride, void* stream);
 
 /* ------------------------------------------------------------------------------------
- * Attention softmax (the middle of SDPA, $TF/models/wav2vec2/modeling_wav2vec2.py:438-463,
- * $TF/models/whisper/modeling_whisper.py:215-238).  scores fp32 [BH, Tq, ld] (alpha already
- * applied by the GEMM), key padding by klen[b] (b = bh / H), optional causal mask;
- * probs bf16 [BH, Tq, ld] with columns >= Tk written as zero (so it can feed a KMAJOR GEMM).
- * bwd: ds = p * (dp - sum_j dp_j p_j) * scale, bf16, zero padded.
- * ---------------------------------------------------------------------------------- */
-int ca_softmax_fwd(const float* scores, void* probs, const int32_t* klen, int32_t BH,
-                   int32_t H, int32_t Tq, int32_t Tk, int64_t ld, int32_t causal,
-                   void* stream);
-int ca_softmax_bwd(const float* dprobs, const void* probs, void* dscores, float scale,
-                   int32_t BH, int32_t Tq, int32_t Tk, int64_t ld, void* stream);
-
-/* ------------------------------------------------------------------------------------
  * Fused multi-head attention (flash-style, no [T,T] matrix in HBM): forward and backward.
  *   $TF/models/wav2vec2/modeling_wav2vec2.py:438-463,529-543 (SDPA) and
  *   $TF/models/whisper/modeling_whisper.py:215-238,284-356.

@@ -265,36 +265,6 @@ def test_col2im(ops):
     assert (dx.float().cpu() - want).abs().max() < 0.02
 
 
-def test_softmax_fwd_bwd(ops):
-    B, H, T, ld = 2, 3, 499, 504
-    s = rnd(B * H, T, ld, seed=1, scale=3.0)
-    klen = torch.tensor([499, 300], dtype=torch.int32)
-    p = torch.empty(B * H, T, ld, dtype=torch.bfloat16, device=DEV)
-    ops.softmax_fwd(s.to(DEV), p, klen.to(DEV), B * H, H, T, T, ld)
-    pc = p.float().cpu()
-    for bh in range(B * H):
-        kl = int(klen[bh // H])
-        want = torch.softmax(s[bh, :, :kl], -1)
-        assert (pc[bh, :, :kl] - want).abs().max() < 4e-3
-        assert (pc[bh, :, kl:] == 0).all()
-    # causal variant
-    ops.softmax_fwd(s.to(DEV), p, None, B * H, H, T, T, ld, causal=True)
-    pc2 = p.float().cpu()
-    i = torch.arange(T)
-    mask = i[None, :] <= i[:, None]
-    want = torch.softmax(s[0, :, :T].masked_fill(~mask, float("-inf")), -1)
-    assert (pc2[0, :, :T] - want).abs().max() < 4e-3
-    # backward
-    dp = rnd(B * H, T, ld, seed=2)
-    ds = torch.empty_like(p)
-    ops.softmax_fwd(s.to(DEV), p, klen.to(DEV), B * H, H, T, T, ld)
-    ops.softmax_bwd(dp.to(DEV), p, ds, 0.125, B * H, T, T, ld)
-    pf = p.float().cpu()
-    want = pf * (dp - (dp[..., :T] * pf[..., :T]).sum(-1, keepdim=True)) * 0.125
-    assert (ds.float().cpu()[..., :T] - want[..., :T]).abs().max() < 5e-3
-    assert (ds.float().cpu()[..., T:] == 0).all()
-
-
 def test_ctc_matches_golden_and_torch(ops, golden_dir):
     z = np.load(golden_dir / "ctc_cases.npz")
     for i in range(int(z["n_cases"])):

@@ -2,13 +2,22 @@
 of libcoral_amd kernels, and the backward schedule of a stack of pre-LN encoder layers (encoder_backward).
 The three block kinds are exactly the ones of `WhisperEncoderLayer` / `WhisperDecoderLayer`
 ($TF/models/whisper/modeling_whisper.py:379-413, 448-505): residual self-attention, residual cross-attention,
-residual GELU feed-forward.  The Whisper training path builds its encoder and decoder layers from them; the
+residual GELU feed-forward.  The Whisper engines build their encoder and decoder layers from them (the training
+forward, `encode`, the teacher-forced `decode` and the feed-forward of the incremental decoding paths); the
 wav2vec2 engine its XLS-R encoder layers (the stable-LayerNorm layer, $TF/models/wav2vec2/modeling_wav2vec2.py:
 611-654, is the same pre-LN self-attention + feed-forward pair).
 
 Every block works on flat row-major bf16 activations [B*T, d] and a `ParamStore` (fp32 masters `p32`,
 bf16 compute copies `p16`, fp32 gradients `g32`); weight gradients are accumulated in fp32.  Workspaces come
-from the caller's allocator z(n, dt=torch.bfloat16) (zero-filled).
+from the caller's allocator z(n, dt=torch.bfloat16) (zero-filled).  alloc(..., train=False) is the inference form:
+the buffers only a backward reads (LayerNorm statistics, Dq, the FFN pre-activation) are None, a forward into it
+writes only what its next launch consumes and keeps nothing for a backward, and the FFN of M <= 128 rows runs its
+LayerNorm inside fc1's prologue (LN_IN_GEMM).
+
+fp8: a forward takes its e4m3 operands per call, dict(w=(p8, scale, x8, rs)) for q|k|v / fc1 (the
+e4m3 weights, the matrix's dequantisation factor, the LayerNorm output as e4m3 and its row scales); the training
+forward adds out= / fc2= (the attention / GELU output as e4m3, see WhisperTrainEngine._train_ws) and bwd= / du= (the
+fp8 data gradients), which the backward finds in the saved states.
 """
 
 from __future__ import annotations
@@ -19,6 +28,11 @@ import torch
 
 from . import ops
 from .ops import EPI_DGELU, EPI_GELU, EPI_RESIDUAL, MNMAJOR
+
+
+# A decoded token's LayerNorms inside the following projection's prologue (CA_DECODE_LN_FUSED=0: their own launches -
+# the A/B switch; the results are bit-identical): the inference FFN of M <= 128 rows, and the incremental decoding paths
+LN_IN_GEMM = os.environ.get("CA_DECODE_LN_FUSED", "1") != "0"
 
 
 def _z(n, dev, dt=torch.bfloat16):
@@ -100,52 +114,52 @@ class SelfAttnBlock:
         # grouped weight-gradient launch); the encoder layout, a decoder layer sets its own
         self.cs_qkv, self.cs_o = 0, 3 * d
 
-    def alloc(self, B, T, z):
+    def alloc(self, B, T, z, train=True):
         d, H = self.d, self.H
         Tqp = (T + 31) // 32 * 32
-        return dict(x=z(B * T * d), st=z(B * T * 2, torch.float32), qkv=z(B * T * 3 * d), ctx=z(B * T * d),
-                    lse=z(B * H * Tqp, torch.float32), Dq=z(B * H * Tqp, torch.float32), Tqp=Tqp)
+        return dict(x=z(B * T * d), st=z(B * T * 2, torch.float32) if train else None, qkv=z(B * T * 3 * d),
+                    ctx=z(B * T * d), lse=z(B * H * Tqp, torch.float32),
+                    Dq=z(B * H * Tqp, torch.float32) if train else None, Tqp=Tqp)
 
-    def _akw(self, B, T, sv, klen):
+    def _akw(self, B, T, Tqp, klen, adrop):
         d, H = self.d, self.H
         hd = d // H
-        ap, aseed = sv.get("adrop", (0.0, 0))
-        return dict(B=B, H=H, Tq=T, Tk=T, hd=hd, Tqp=sv["Tqp"], scale=hd ** -0.5, ldq=3 * d, ldk=3 * d, ldv=3 * d, ldo=d,
+        return dict(B=B, H=H, Tq=T, Tk=T, hd=hd, Tqp=Tqp, scale=hd ** -0.5, ldq=3 * d, ldk=3 * d, ldv=3 * d, ldo=d,
                     sqb=T * 3 * d, skb=T * 3 * d, svb=T * 3 * d, sob=T * d, q_off=0, k_off=d, v_off=2 * d, klen=klen,
-                    causal=self.causal, dropout_p=ap, dropout_seed=aseed)
+                    causal=self.causal, dropout_p=adrop[0], dropout_seed=adrop[1])
 
-    def forward(self, hin, hout, sv, B, T, klen=None, hdrop=(0.0, 0), adrop=(0.0, 0)):
+    def forward(self, hin, hout, sv, B, T, klen=None, hdrop=(0.0, 0), adrop=(0.0, 0), fp8=None):
         """hdrop: (p, seed) of the hidden-state dropout on the block's output; adrop: of the dropout on the attention
-        probabilities ($TF/models/whisper/modeling_whisper.py:234)."""
+        probabilities ($TF/models/whisper/modeling_whisper.py:234); fp8: this call's e4m3 operands (module docstring)."""
         st, d = self.st, self.d
         M = B * T
-        sv["adrop"] = adrop
-        fp8 = getattr(self, "fp8", None)  # (p8, scale, x8, rs): forward projection on the fp8 path (DESIGN.md 4.4)
+        train = sv["st"] is not None
         if fp8 is not None:
-            p8, scale, x8, rs = fp8
-            ops.layernorm_fwd_fp8(hin, st.view(self.ln + ".weight"), st.view(self.ln + ".bias"), sv["x"], x8, rs, M, d, self.eps,
-                                  stats=sv["st"])
+            p8, scale, x8, rs = fp8["w"]
+            ops.layernorm_fwd_fp8(hin, st.view(self.ln + ".weight"), st.view(self.ln + ".bias"), sv["x"] if train else None,
+                                  x8, rs, M, d, self.eps, stats=sv["st"])
             ops.gemm_fp8(x8, p8, sv["qkv"], a_row_scale=rs, b_scale=scale, M=M, N=3 * d, K=d, lda=d, ldb=d, ldc=3 * d,
                          b_off=st.off(self.attn + "q_proj.weight"), bias=st.p32, bias_off=st.off(self.qbias))
         else:
             ops.layernorm_fwd(hin, st.view(self.ln + ".weight"), st.view(self.ln + ".bias"), sv["x"], sv["st"], M, d, self.eps)
             ops.gemm(sv["x"], st.p16, sv["qkv"], M=M, N=3 * d, K=d, lda=d, ldb=d, ldc=3 * d,
                      b_off=st.off(self.attn + "q_proj.weight"), bias=st.p32, bias_off=st.off(self.qbias))
-        o8 = getattr(self, "fp8_out", None) if (fp8 is not None and T >= 100 and adrop[0] == 0.0) else None
+        akw = self._akw(B, T, sv["Tqp"], klen, adrop)
+        o8 = fp8.get("out") if (fp8 is not None and T >= 100 and adrop[0] == 0.0) else None
         if o8 is not None:
             # out_proj on the fp8 path: the attention kernel's output stage also writes the context as e4m3 (delayed
             # per-tensor scale, CaAttnDesc.O8)
-            ops.attn_fwd(sv["qkv"], sv["qkv"], sv["qkv"], sv["ctx"], sv["lse"], O8=o8[0], o8_scale=o8[1], o8_amax=o8[3],
-                         **self._akw(B, T, sv, klen))
-            ops.gemm_fp8(o8[0], fp8[0], hout, a_scale=o8[2], b_scale=o8[4], M=M, N=d, K=d, lda=d, ldb=d, ldc=d,
+            ops.attn_fwd(sv["qkv"], sv["qkv"], sv["qkv"], sv["ctx"], sv["lse"], O8=o8[0], o8_scale=o8[1], o8_amax=o8[3], **akw)
+            ops.gemm_fp8(o8[0], p8, hout, a_scale=o8[2], b_scale=o8[4], M=M, N=d, K=d, lda=d, ldb=d, ldc=d,
                          b_off=st.off(self.attn + "out_proj.weight"), bias=st.p32, bias_off=st.off(self.attn + "out_proj.bias"),
                          epilogue=EPI_RESIDUAL, R=hin, ldr=d, dropout_p=hdrop[0], dropout_seed=hdrop[1])
         else:
-            ops.attn_fwd(sv["qkv"], sv["qkv"], sv["qkv"], sv["ctx"], sv["lse"], **self._akw(B, T, sv, klen))
+            ops.attn_fwd(sv["qkv"], sv["qkv"], sv["qkv"], sv["ctx"], sv["lse"], **akw)
             ops.gemm(sv["ctx"], st.p16, hout, M=M, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=st.off(self.attn + "out_proj.weight"),
                      bias=st.p32, bias_off=st.off(self.attn + "out_proj.bias"), epilogue=EPI_RESIDUAL, R=hin, ldr=d,
                      dropout_p=hdrop[0], dropout_seed=hdrop[1])
-        sv["hin"], sv["klen"], sv["hdrop"] = hin, klen, hdrop
+        if train:
+            sv.update(hin=hin, klen=klen, hdrop=hdrop, adrop=adrop, fp8=fp8)
 
     def backward(self, dh, dhin, sv, sc: Scratch, B, T, defer=None, acc=True, sq=None, ln_part=None, pending=None,
                  dy=None, xdrop=None, deferred=None):
@@ -162,7 +176,7 @@ class SelfAttnBlock:
         st, d = self.st, self.d
         M = B * T
         o, g32, p16 = st.off, st.g32, st.p16
-        fb = getattr(self, "fp8_bwd", None) if getattr(self, "fp8", None) is not None else None
+        fb = sv["fp8"].get("bwd") if sv["fp8"] is not None else None
         if dy is None:
             dy = _masked_grad(dh, sv, sc, M * d, "attn") if fb is None else _masked_grad_fp8(dh, sv, sc, M, d, "attn", fb)
         # with `defer` the bias gradients travel with the problems (fused into the grouped launch or done by it)
@@ -178,7 +192,7 @@ class SelfAttnBlock:
         qkv, dqkv = sv["qkv"], sc.dqkv
         ops.attn_bwd(qkv, qkv, qkv, sv["ctx"], sv["lse"], sc.dctx, sv["Dq"], dqkv, dqkv, dqkv, lddo=d, sdob=T * d, lddq=3 * d,
                      lddk=3 * d, lddv=3 * d, sdqb=T * 3 * d, sdkb=T * 3 * d, sdvb=T * 3 * d, dq_off=0, dk_off=d, dv_off=2 * d,
-                     **self._akw(B, T, sv, sv["klen"]))
+                     **self._akw(B, T, sv["Tqp"], sv["klen"], sv["adrop"]))
         if defer is None:
             ops.colsum(dqkv, 3 * d, M, 3 * d, g32, sc.part, out_off=o(self.qbias))
         wg.append(dict(dY=dqkv, X=sv["x"], M=3 * d, N=d, K=M, lda=3 * d, ldb=d, c_off=o(self.attn + "q_proj.weight"),
@@ -200,38 +214,43 @@ class CrossAttnBlock:
     def __init__(self, store, ln: str, attn: str, H: int, d: int, eps: float):
         self.st, self.ln, self.attn, self.H, self.d, self.eps = store, ln, attn, H, d, eps
 
-    def alloc(self, B, L, Te, dev):
+    def alloc(self, B, L, Te, z, train=True):
+        """(train=False: no K|V buffer either - the forward then takes the caller's, `kv=`)"""
         d, H = self.d, self.H
         Lqp = (L + 31) // 32 * 32
-        return dict(x=_z(B * L * d, dev), st=_z(B * L * 2, dev, torch.float32), q=_z(B * L * d, dev), ctx=_z(B * L * d, dev),
-                    kv=_z(B * Te * 2 * d, dev), lse=_z(B * H * Lqp, dev, torch.float32), Dq=_z(B * H * Lqp, dev, torch.float32),
-                    Tqp=Lqp)
+        return dict(x=z(B * L * d), st=z(B * L * 2, torch.float32) if train else None, q=z(B * L * d), ctx=z(B * L * d),
+                    kv=z(B * Te * 2 * d) if train else None, lse=z(B * H * Lqp, torch.float32),
+                    Dq=z(B * H * Lqp, torch.float32) if train else None, Tqp=Lqp)
 
-    def _akw(self, B, L, Te, sv):
+    def _akw(self, B, L, Te, Tqp, adrop):
         d, H = self.d, self.H
         hd = d // H
-        ap, aseed = sv.get("adrop", (0.0, 0))
-        return dict(B=B, H=H, Tq=L, Tk=Te, hd=hd, Tqp=sv["Tqp"], scale=hd ** -0.5, ldq=d, ldk=2 * d, ldv=2 * d, ldo=d,
-                    sqb=L * d, skb=Te * 2 * d, svb=Te * 2 * d, sob=L * d, k_off=0, v_off=d, dropout_p=ap, dropout_seed=aseed)
+        return dict(B=B, H=H, Tq=L, Tk=Te, hd=hd, Tqp=Tqp, scale=hd ** -0.5, ldq=d, ldk=2 * d, ldv=2 * d, ldo=d,
+                    sqb=L * d, skb=Te * 2 * d, svb=Te * 2 * d, sob=L * d, k_off=0, v_off=d, dropout_p=adrop[0],
+                    dropout_seed=adrop[1])
 
     def project_kv(self, enc, sv, B, Te):
+        """K|V of the encoder states into sv["kv"] (returned)."""
         st, d = self.st, self.d
         ops.gemm(enc, st.p16, sv["kv"], M=B * Te, N=2 * d, K=d, lda=d, ldb=d, ldc=2 * d, b_off=st.off(self.attn + "k_proj.weight"),
                  bias=st.p32, bias_off=st.off(self.attn + "k_proj.bias__zero"))
         sv["enc"] = enc
+        return sv["kv"]
 
-    def forward(self, hin, hout, sv, B, L, Te, hdrop=(0.0, 0), adrop=(0.0, 0)):
+    def forward(self, hin, hout, sv, B, L, Te, kv=None, hdrop=(0.0, 0), adrop=(0.0, 0)):
+        """kv: the K|V of the encoder states (default: sv["kv"], project_kv's)."""
         st, d = self.st, self.d
         M = B * L
-        sv["adrop"] = adrop
+        kv = sv["kv"] if kv is None else kv
         ops.layernorm_fwd(hin, st.view(self.ln + ".weight"), st.view(self.ln + ".bias"), sv["x"], sv["st"], M, d, self.eps)
         ops.gemm(sv["x"], st.p16, sv["q"], M=M, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=st.off(self.attn + "q_proj.weight"),
                  bias=st.p32, bias_off=st.off(self.attn + "q_proj.bias"))
-        ops.attn_fwd(sv["q"], sv["kv"], sv["kv"], sv["ctx"], sv["lse"], **self._akw(B, L, Te, sv))
+        ops.attn_fwd(sv["q"], kv, kv, sv["ctx"], sv["lse"], **self._akw(B, L, Te, sv["Tqp"], adrop))
         ops.gemm(sv["ctx"], st.p16, hout, M=M, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=st.off(self.attn + "out_proj.weight"),
                  bias=st.p32, bias_off=st.off(self.attn + "out_proj.bias"), epilogue=EPI_RESIDUAL, R=hin, ldr=d,
                  dropout_p=hdrop[0], dropout_seed=hdrop[1])
-        sv["hin"], sv["hdrop"] = hin, hdrop
+        if sv["st"] is not None:
+            sv.update(hin=hin, hdrop=hdrop, adrop=adrop)
 
     def backward(self, dh, dhin, sv, sc: Scratch, denc32, B, L, Te, defer=None, cs=(0, 0), ln_part=None, pending=None,
                  acc=True):
@@ -254,7 +273,7 @@ class CrossAttnBlock:
         dq, dkv = (sc.dx if defer is None else sc.dq), sc.dkv
         ops.attn_bwd(sv["q"], sv["kv"], sv["kv"], sv["ctx"], sv["lse"], sc.dctx, sv["Dq"], dq, dkv, dkv, lddo=d, sdob=L * d,
                      lddq=d, lddk=2 * d, lddv=2 * d, sdqb=L * d, sdkb=Te * 2 * d, sdvb=Te * 2 * d, dk_off=0, dv_off=d,
-                     **self._akw(B, L, Te, sv))
+                     **self._akw(B, L, Te, sv["Tqp"], sv["adrop"]))
         # q projection
         if defer is None:
             ops.colsum(dq, d, M, d, g32, sc.part, out_off=o(self.attn + "q_proj.bias"))
@@ -280,36 +299,41 @@ class FFNBlock:
         self.st, self.ln, self.fc1, self.fc2, self.d, self.f, self.eps = store, ln, fc1, fc2, d, f, eps
         self.cs_fc1, self.cs_fc2 = 4 * d, 4 * d + f  # (the encoder layer's bias vector; see SelfAttnBlock)
 
-    def alloc(self, M, z):
-        return dict(x=z(M * self.d), st=z(M * 2, torch.float32), u=z(M * self.f), g=z(M * self.f))
+    def alloc(self, M, z, train=True):
+        """(train=False: no pre-activation u either - fc1 then writes only the GELU output)"""
+        return dict(x=z(M * self.d), st=z(M * 2, torch.float32) if train else None, u=z(M * self.f) if train else None,
+                    g=z(M * self.f))
 
-    def forward(self, hin, hout, sv, M, dropout_p=0.0, seed=0, hdrop=(0.0, 0)):
+    def forward(self, hin, hout, sv, M, dropout_p=0.0, seed=0, hdrop=(0.0, 0), fp8=None):
         st, d, f = self.st, self.d, self.f
-        fp8 = getattr(self, "fp8", None)
-        fc2_8 = getattr(self, "fp8_fc2", None) if fp8 is not None else None
+        train = sv["st"] is not None
+        gamma, beta = st.view(self.ln + ".weight"), st.view(self.ln + ".bias")
+        fc1 = dict(M=M, N=f, K=d, lda=d, ldb=d, ldc=f, b_off=st.off(self.fc1 + ".weight"), bias=st.p32,
+                   bias_off=st.off(self.fc1 + ".bias"), epilogue=EPI_GELU, dropout_p=dropout_p, dropout_seed=seed,
+                   stream_out=train and ops.STREAM_U)
+        fc2_8 = fp8.get("fc2") if fp8 is not None else None
         if fp8 is not None:
-            p8, scale, x8, rs = fp8
-            ops.layernorm_fwd_fp8(hin, st.view(self.ln + ".weight"), st.view(self.ln + ".bias"), sv["x"], x8, rs, M, d, self.eps,
-                                  stats=sv["st"])
+            p8, scale, x8, rs = fp8["w"]
+            ops.layernorm_fwd_fp8(hin, gamma, beta, sv["x"] if train else None, x8, rs, M, d, self.eps, stats=sv["st"])
             # (fc2 on the fp8 path: the GELU output also leaves fc1's epilogue as e4m3, delayed per-tensor scale)
             c8 = dict(C8=fc2_8[0], c8_scale=fc2_8[1], c8_amax=fc2_8[3]) if fc2_8 is not None else {}
-            ops.gemm_fp8(x8, p8, sv["u"], C2=sv["g"], a_row_scale=rs, b_scale=scale, M=M, N=f, K=d, lda=d, ldb=d, ldc=f,
-                         b_off=st.off(self.fc1 + ".weight"), bias=st.p32, bias_off=st.off(self.fc1 + ".bias"),
-                         epilogue=EPI_GELU, dropout_p=dropout_p, dropout_seed=seed, stream_out=ops.STREAM_U, **c8)
+            ops.gemm_fp8(x8, p8, sv["u"], C2=sv["g"], a_row_scale=rs, b_scale=scale, **fc1, **c8)
+        elif not train and M <= 128 and d <= 2048 and LN_IN_GEMM:
+            # a decoded token: the LayerNorm runs in fc1's prologue (CaGemmDesc.a_ln_gamma, bit-identical)
+            ops.gemm(hin, st.p16, None, C2=sv["g"], a_ln=(gamma, beta, self.eps), **fc1)
         else:
-            ops.layernorm_fwd(hin, st.view(self.ln + ".weight"), st.view(self.ln + ".bias"), sv["x"], sv["st"], M, d, self.eps)
-            ops.gemm(sv["x"], st.p16, sv["u"], C2=sv["g"], M=M, N=f, K=d, lda=d, ldb=d, ldc=f, b_off=st.off(self.fc1 + ".weight"),
-                     bias=st.p32, bias_off=st.off(self.fc1 + ".bias"), epilogue=EPI_GELU, dropout_p=dropout_p,
-                     dropout_seed=seed, stream_out=ops.STREAM_U)
+            ops.layernorm_fwd(hin, gamma, beta, sv["x"], sv["st"], M, d, self.eps)
+            ops.gemm(sv["x"], st.p16, sv["u"], C2=sv["g"], **fc1)
         if fc2_8 is not None:
-            ops.gemm_fp8(fc2_8[0], fp8[0], hout, a_scale=fc2_8[2], b_scale=fc2_8[4], M=M, N=d, K=f, lda=f, ldb=f, ldc=d,
+            ops.gemm_fp8(fc2_8[0], p8, hout, a_scale=fc2_8[2], b_scale=fc2_8[4], M=M, N=d, K=f, lda=f, ldb=f, ldc=d,
                          b_off=st.off(self.fc2 + ".weight"), bias=st.p32, bias_off=st.off(self.fc2 + ".bias"),
                          epilogue=EPI_RESIDUAL, R=hin, ldr=d, dropout_p=hdrop[0], dropout_seed=hdrop[1])
         else:
             ops.gemm(sv["g"], st.p16, hout, M=M, N=d, K=f, lda=f, ldb=f, ldc=d, b_off=st.off(self.fc2 + ".weight"), bias=st.p32,
                      bias_off=st.off(self.fc2 + ".bias"), epilogue=EPI_RESIDUAL, R=hin, ldr=d, dropout_p=hdrop[0],
                      dropout_seed=hdrop[1])
-        sv["hin"], sv["drop"], sv["hdrop"] = hin, (dropout_p, seed), hdrop
+        if train:
+            sv.update(hin=hin, drop=(dropout_p, seed), hdrop=hdrop, fp8=fp8)
 
     def backward(self, dh, dhin, sv, sc: Scratch, M, defer=None, acc=True, sq=None, ln_part=None, pending=None, dy=None,
                  xdrop=None):
@@ -318,7 +342,7 @@ class FFNBlock:
         st, d, f = self.st, self.d, self.f
         o, g32, p16 = st.off, st.g32, st.p16
         p, seed = sv["drop"]
-        fb = getattr(self, "fp8_bwd", None) if getattr(self, "fp8", None) is not None else None
+        fb = sv["fp8"].get("bwd") if sv["fp8"] is not None else None
         if dy is None:
             dy = _masked_grad(dh, sv, sc, M * d, "ffn") if fb is None else _masked_grad_fp8(dh, sv, sc, M, d, "ffn", fb)
         if defer is None:
@@ -326,7 +350,7 @@ class FFNBlock:
         wg = [dict(dY=dy, X=sv["g"], M=d, N=f, K=M, lda=d, ldb=f, c_off=o(self.fc2 + ".weight"), accumulate=acc,
                    sq=sq.get("fc2"),
                    **(dict(bias_off=o(self.fc2 + ".bias"), part=sc.part, cs_off=self.cs_fc2) if defer is not None else {}))]
-        du8 = getattr(self, "fp8_du", None) if fb is not None else None
+        du8 = sv["fp8"].get("du") if fb is not None else None
         if fb is not None:  # fc2's data gradient on the fp8 path (GELU' epilogue as on the bf16 path)
             # (fc1's data gradient on it too: dU also leaves this epilogue as e4m3, delayed per-tensor scale - CaGemmDesc.C8)
             c8 = dict(C8=du8["buf"], c8_scale=du8["scale"], c8_amax=du8["amax"]) if du8 is not None else {}

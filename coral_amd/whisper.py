@@ -9,12 +9,12 @@ pipeline calls (R/src/coral/evaluate.py:56-60 -> `model.generate`):
   WhisperForConditionalGeneration    :994-1099 (shift_tokens_right, tied proj_out, CE ignore -100)
   greedy generate                    $TF/models/whisper/generation_whisper.py:383,1455,1774-1812
 
-Round-1 scope: forward paths (inference, evaluation loss, greedy decode).  The conv stem runs as
-overlapping-row GEMMs over a time-padded channels-last buffer (Conv1d k=3, p=1, stride 1 / 2), the
-sinusoidal positions are added in the second conv's epilogue, layers reuse the wav2vec2 kernels
-(the encoder layer is the same pre-LN block), the decoder adds causal and cross attention.
-Greedy decoding re-runs the decoder over the growing prefix with the cross-attention K/V computed
-once per clip (a KV-cached single-token step and the Whisper backward are the next items).
+Forward paths (inference, evaluation loss, greedy decode).  The conv stem runs as overlapping-row GEMMs
+over a time-padded channels-last buffer (Conv1d k=3, p=1, stride 1 / 2), the sinusoidal positions are
+added in the second conv's epilogue.  The encoder and decoder layers are the pre-LN blocks of blocks.py,
+run on inference workspaces; the training engine (whisper_train.py) runs the same blocks, stem and head
+with saved activations.  Greedy decoding appends one token at a time against a self-attention K|V cache
+(decode_step, or the graph-replayed / persistent token step), the cross-attention K|V computed once per clip.
 """
 
 from __future__ import annotations
@@ -27,7 +27,8 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .ops import EPI_GELU, EPI_GELU_RESIDUAL, EPI_NONE, EPI_RESIDUAL, KMAJOR, MNMAJOR
+from .blocks import LN_IN_GEMM, CrossAttnBlock, FFNBlock, SelfAttnBlock, zeros_on
+from .ops import EPI_GELU, EPI_GELU_RESIDUAL, EPI_RESIDUAL
 from .wav2vec2 import ParamStore, _r8
 
 
@@ -49,10 +50,6 @@ class WhisperShape:
     eos_token_id: int = 50257
     layer_norm_eps: float = 1e-5
 
-
-# A decoded token's self-attention and FFN LayerNorms inside the following projection's prologue (CA_DECODE_LN_FUSED=0:
-# their own launches - the A/B switch; the results are bit-identical)
-LN_IN_GEMM = os.environ.get("CA_DECODE_LN_FUSED", "1") != "0"
 
 # CoRal model keys -> architectures (R/config/model/whisper-*.yaml:3-5; public config.json values)
 CORAL_WHISPER_SHAPES = {
@@ -139,6 +136,16 @@ def whisper_param_list(s: WhisperShape):
     return out
 
 
+def shift_tokens_right(labels: torch.Tensor, pad_token_id: int, decoder_start_token_id: int) -> torch.Tensor:
+    """Decoder inputs of teacher forcing ($TF/models/whisper/modeling_whisper.py, shift_tokens_right): the labels one
+    position to the right behind the start token, -100 replaced by the pad token."""
+    lab = labels.to(torch.int64)
+    dec = lab.new_zeros(lab.shape)
+    dec[:, 1:] = lab[:, :-1]
+    dec[:, 0] = decoder_start_token_id
+    return dec.masked_fill(dec == -100, pad_token_id)
+
+
 def sinusoid_positions(length: int, channels: int, max_timescale: float = 10000.0) -> torch.Tensor:
     """The encoder's fixed position table ($TF/models/whisper/modeling_whisper.py:55-64): [sin | cos] of
     position x geometric timescales."""
@@ -165,6 +172,23 @@ class WhisperEngine:
         self.conv1_wr = torch.zeros(d * 3 * shape.num_mel_bins, dtype=torch.bfloat16, device=self.device)
         self.conv2_wr = torch.zeros(d * 3 * d, dtype=torch.bfloat16, device=self.device)
         self.mel_filters = torch.from_numpy(mel_filter_bank(shape.num_mel_bins)).to(self.device)
+        self.zero_mel = torch.zeros(shape.num_mel_bins, dtype=torch.bfloat16, device=self.device)  # SpecAugment's fill
+        st, eps = self.store, shape.layer_norm_eps
+
+        def self_attn_ffn(p, H, f, causal):  # the self-attention and feed-forward blocks of layer `p`
+            return (SelfAttnBlock(st, p + "self_attn_layer_norm", p + "self_attn.", H, d, eps, causal, p + "self_attn.q_proj.bias"),
+                    FFNBlock(st, p + "final_layer_norm", p + "fc1", p + "fc2", d, f, eps))
+
+        self.enc_blocks = [self_attn_ffn(f"model.encoder.layers.{l}.", shape.encoder_attention_heads, shape.encoder_ffn_dim,
+                                         False) for l in range(shape.encoder_layers)]
+        self.dec_blocks = []
+        for l in range(shape.decoder_layers):
+            p = f"model.decoder.layers.{l}."
+            sa, ff = self_attn_ffn(p, shape.decoder_attention_heads, shape.decoder_ffn_dim, True)
+            ca = CrossAttnBlock(st, p + "encoder_attn_layer_norm", p + "encoder_attn.", shape.decoder_attention_heads, d, eps)
+            # a decoder layer's bias vector (whisper_param_list): self q|k|v, self out, cross q, cross k|v, cross out, fc1, fc2
+            sa.cs_qkv, sa.cs_o, ca.cs, ff.cs_fc1, ff.cs_fc2 = 0, 3 * d, (4 * d, 7 * d), 8 * d, 8 * d + shape.decoder_ffn_dim
+            self.dec_blocks.append((sa, ca, ff))
         self._enc_ws = {}
         self._dec_ws = {}
 
@@ -214,46 +238,65 @@ class WhisperEngine:
         ops.logmel(x, self.mel_filters, out, ws, B, N, self.s.num_mel_bins)
         return out
 
-    # ---- shared blocks -----------------------------------------------------------------------
-    def _lse(self, n):
-        if getattr(self, "_lse_buf", None) is None or self._lse_buf.numel() < n:
-            self._lse_buf = torch.zeros(n, dtype=torch.float32, device=self.device)
-        return self._lse_buf
-
-    def _self_attention(self, qkv, ctx, B, T, H, hd, d, causal):
-        Tqp = (T + 31) // 32 * 32
-        ops.attn_fwd(qkv, qkv, qkv, ctx, self._lse(B * H * Tqp), B=B, H=H, Tq=T, Tk=T, hd=hd, Tqp=Tqp,
-                     scale=hd ** -0.5, ldq=3 * d, ldk=3 * d, ldv=3 * d, ldo=d, sqb=T * 3 * d, skb=T * 3 * d,
-                     svb=T * 3 * d, sob=T * d, q_off=0, k_off=d, v_off=2 * d, causal=causal)
-
-    def _ffn(self, w, h_in, h_out, p, M, d, f):
-        st, p32, p16 = self.store, self.store.p32, self.store.p16
+    # ---- shared pieces -----------------------------------------------------------------------
+    def encoder_stem(self, x, w, h, pre=(None, None), mask_time=None, mask_feature=None):
+        """x f32 [B, mels, 3000] -> h = gelu(conv2(gelu(conv1(x)))) + positions, bf16 [B*1500, d].  w["xin"] / w["c1"]:
+        the time-padded channels-last input and conv1's output ([B, 3002, mels | d] + 64).  pre: where the training
+        forward keeps the two pre-activations (None: not written); mask_time / mask_feature: SpecAugment masks on the
+        device, u8 [B, 3000] / [B, mels]."""
+        s, st = self.s, self.store
         o = st.off
-        if M <= 128 and d <= 2048 and LN_IN_GEMM:
-            # a decoded token: the LayerNorm runs in the projection's prologue (CaGemmDesc.a_ln_gamma, bit-identical)
-            ops.gemm(h_in, p16, None, C2=w["g"], M=M, N=f, K=d, lda=d, ldb=d, ldc=f, b_off=o(p + "fc1.weight"),
-                     bias=p32, bias_off=o(p + "fc1.bias"), epilogue=EPI_GELU,
-                     a_ln=(st.view(p + "final_layer_norm.weight"), st.view(p + "final_layer_norm.bias"), self.s.layer_norm_eps))
-        else:
-            ops.layernorm_fwd(h_in, st.view(p + "final_layer_norm.weight"), st.view(p + "final_layer_norm.bias"),
-                              w["x"], None, M, d, self.s.layer_norm_eps)
-            ops.gemm(w["x"], p16, None, C2=w["g"], M=M, N=f, K=d, lda=d, ldb=d, ldc=f, b_off=o(p + "fc1.weight"),
-                     bias=p32, bias_off=o(p + "fc1.bias"), epilogue=EPI_GELU)
-        ops.gemm(w["g"], p16, h_out, M=M, N=d, K=f, lda=f, ldb=f, ldc=d, b_off=o(p + "fc2.weight"), bias=p32,
-                 bias_off=o(p + "fc2.bias"), epilogue=EPI_RESIDUAL, R=h_in, ldr=d)
+        B, mels, Tin = x.shape
+        T, d = s.max_source_positions, s.d_model
+        # channels-last, time-padded input: rows 1..3000 of each clip hold the frames
+        for b in range(B):
+            ops.transpose_f32_bf16(x[b], w["xin"][(b * (Tin + 2) + 1) * mels:], mels, Tin)
+            if mask_time is not None or mask_feature is not None:  # SpecAugment on the input features
+                tm = mask_time[b:b + 1].contiguous() if mask_time is not None else None
+                fm = mask_feature[b:b + 1].contiguous() if mask_feature is not None else None
+                ops.mask_frames(w["xin"][(b * (Tin + 2) + 1) * mels:], tm, fm, self.zero_mel, None, 1, Tin, mels)
+        # conv1 (k=3, p=1) + GELU -> padded [B, 3002, d]
+        ops.gemm(w["xin"], self.conv1_wr, pre[0], C2=w["c1"], c_off=d, c2_off=d, M=Tin, N=d, K=3 * mels, lda=mels,
+                 ldb=3 * mels, ldc=d, bias=st.p32, bias_off=o("model.encoder.conv1.bias"), epilogue=EPI_GELU, batch2=B,
+                 sA=(0, (Tin + 2) * mels), sC=(0, (Tin + 2) * d))
+        # conv2 (k=3, s=2, p=1) + GELU + sinusoidal positions
+        ops.gemm(w["c1"], self.conv2_wr, pre[1], C2=h, M=T, N=d, K=3 * d, lda=2 * d, ldb=3 * d, ldc=d, bias=st.p32,
+                 bias_off=o("model.encoder.conv2.bias"), epilogue=EPI_GELU_RESIDUAL, R=st.p16,
+                 r_off=o("model.encoder.embed_positions.weight"), ldr=d, batch2=B, sA=(0, (Tin + 2) * d), sC=(0, T * d),
+                 sR=(0, 0))
+
+    def _embed(self, ids, pos, h, M):
+        """The decoder's input rows: token + position embeddings of int32 ids / positions on the device."""
+        p16, o = self.store.p16, self.store.off
+        ops.embed_tokens(p16[o("model.decoder.embed_tokens.weight"):], p16[o("model.decoder.embed_positions.weight"):],
+                         ids, pos, h, M, self.s.d_model)
+
+    def _head(self, h, hf, M, logits=None, stats=None, last_of=None):
+        """The decoder's final LayerNorm (h -> hf, M rows) and the tied output projection: fp32 logits [rows, Vp] of every
+        row, or with last_of=B of the last row of each of B sequences, into `logits` (default: a fresh buffer)."""
+        s, st = self.s, self.store
+        d, V, Vp = s.d_model, s.vocab_size, _r8(s.vocab_size)
+        ops.layernorm_fwd(h, st.view("model.decoder.layer_norm.weight"), st.view("model.decoder.layer_norm.bias"), hf, stats,
+                          M, d, s.layer_norm_eps)
+        rows, n = (hf, M) if last_of is None else (hf.view(last_of, M // last_of, d)[:, -1, :].contiguous(), last_of)
+        if logits is None:
+            # (torch.empty: the GEMM writes all V columns, the Vp - V pad columns are never read - no fill kernel per call)
+            logits = torch.empty(n, Vp, dtype=torch.float32, device=self.device)
+        ops.gemm(rows, st.p16, logits, M=n, N=V, K=d, lda=d, ldb=d, ldc=Vp, b_off=st.off("model.decoder.embed_tokens.weight"))
+        return logits
 
     # ---- encoder -----------------------------------------------------------------------------
     def _encoder_ws(self, B):
+        """The stem's buffers, the residual stream and one inference workspace that every layer's blocks reuse."""
         if B in self._enc_ws:
             return self._enc_ws[B]
-        s, dev = self.s, self.device
-        d, f, H, T = s.d_model, s.encoder_ffn_dim, s.encoder_attention_heads, s.max_source_positions
-        Tin = 2 * T
-        Tp = _r8(T)
-        z = lambda n, dt=torch.bfloat16: torch.zeros(n, dtype=dt, device=dev)  # noqa: E731
-        w = dict(xin=z(B * (Tin + 2) * s.num_mel_bins + 64), c1=z(B * (Tin + 2) * d + 64), h=[z(B * T * d), z(B * T * d)],
-                 x=z(B * T * d), qkv=z(B * T * 3 * d), ctx=z(B * T * d), g=z(B * T * f), out=z(B * T * d),
-                 pos16=self.store.p16[self.store.off("model.encoder.embed_positions.weight"):])
+        s = self.s
+        d, T = s.d_model, s.max_source_positions
+        z = zeros_on(self.device)
+        w = dict(xin=z(B * (2 * T + 2) * s.num_mel_bins + 64), c1=z(B * (2 * T + 2) * d + 64), h=[z(B * T * d), z(B * T * d)],
+                 out=z(B * T * d))
+        for sa, ff in self.enc_blocks[:1]:  # (every layer's blocks have the same shapes)
+            w.update(sa=sa.alloc(B, T, z, train=False), ff=ff.alloc(B * T, z, train=False))
         self._enc_ws[B] = w
         return w
 
@@ -285,62 +328,28 @@ class WhisperEngine:
         """input_features f32 [B, mels, 3000] -> encoder states bf16 [B, 1500, d]."""
         self._await_all()
         s, st = self.s, self.store
-        p32, p16, o = st.p32, st.p16, st.off
         x = input_features.to(self.device, torch.float32).contiguous()
         B, mels, Tin = x.shape
-        T = s.max_source_positions
+        T, d = s.max_source_positions, s.d_model
         if mels != s.num_mel_bins or Tin != 2 * T:
             raise ValueError(f"Whisper expects the mel input features to be of shape [B, {s.num_mel_bins}, {2 * T}], "
                              f"but found {tuple(x.shape)}")
-        d, f, H = s.d_model, s.encoder_ffn_dim, s.encoder_attention_heads
-        hd = d // H
-        w = self._encoder_ws(B)
         M = B * T
-        # channels-last, time-padded input: rows 1..3000 of each clip hold the frames
-        for b in range(B):
-            ops.transpose_f32_bf16(x[b], w["xin"][(b * (Tin + 2) + 1) * mels:], mels, Tin)
-        # conv1 (k=3, p=1) + GELU -> padded [B, 3002, d]
-        ops.gemm(w["xin"], self.conv1_wr, None, C2=w["c1"], c2_off=d, M=Tin, N=d, K=3 * mels, lda=mels, ldb=3 * mels,
-                 ldc=d, bias=p32, bias_off=o("model.encoder.conv1.bias"), epilogue=EPI_GELU, batch2=B,
-                 sA=(0, (Tin + 2) * mels), sC=(0, (Tin + 2) * d))
-        # conv2 (k=3, s=2, p=1) + GELU + sinusoidal positions
-        h = w["h"][0]
-        ops.gemm(w["c1"], self.conv2_wr, None, C2=h, M=T, N=d, K=3 * d, lda=2 * d, ldb=3 * d, ldc=d, bias=p32,
-                 bias_off=o("model.encoder.conv2.bias"), epilogue=EPI_GELU_RESIDUAL, R=w["pos16"], ldr=d, batch2=B,
-                 sA=(0, (Tin + 2) * d), sC=(0, T * d), sR=(0, 0))
-        cur = 0
-        for l in range(s.encoder_layers):
-            p = f"model.encoder.layers.{l}."
-            hin, hmid = w["h"][cur], w["h"][1 - cur]
-            fp8 = self._fp8
-            if fp8 is not None:
-                if "x8" not in w:
-                    w["x8"] = torch.zeros(M * d, dtype=torch.uint8, device=self.device)
-                    w["rs"] = torch.zeros(M, dtype=torch.float32, device=self.device)
-                ops.layernorm_fwd_fp8(hin, st.view(p + "self_attn_layer_norm.weight"), st.view(p + "self_attn_layer_norm.bias"),
-                                      None, w["x8"], w["rs"], M, d, s.layer_norm_eps)
-                ops.gemm_fp8(w["x8"], fp8["p8"], w["qkv"], a_row_scale=w["rs"], b_scale=fp8["scales"][2 * l:2 * l + 1],
-                             M=M, N=3 * d, K=d, lda=d, ldb=d, ldc=3 * d, b_off=o(p + "self_attn.q_proj.weight"),
-                             bias=p32, bias_off=o(p + "self_attn.q_proj.bias"))
-            else:
-                ops.layernorm_fwd(hin, st.view(p + "self_attn_layer_norm.weight"), st.view(p + "self_attn_layer_norm.bias"),
-                                  w["x"], None, M, d, s.layer_norm_eps)
-                ops.gemm(w["x"], p16, w["qkv"], M=M, N=3 * d, K=d, lda=d, ldb=d, ldc=3 * d,
-                         b_off=o(p + "self_attn.q_proj.weight"), bias=p32, bias_off=o(p + "self_attn.q_proj.bias"))
-            self._self_attention(w["qkv"], w["ctx"], B, T, H, hd, d, causal=False)
-            ops.gemm(w["ctx"], p16, hmid, M=M, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(p + "self_attn.out_proj.weight"),
-                     bias=p32, bias_off=o(p + "self_attn.out_proj.bias"), epilogue=EPI_RESIDUAL, R=hin, ldr=d)
-            if fp8 is not None:
-                ops.layernorm_fwd_fp8(hmid, st.view(p + "final_layer_norm.weight"), st.view(p + "final_layer_norm.bias"),
-                                      None, w["x8"], w["rs"], M, d, s.layer_norm_eps)
-                ops.gemm_fp8(w["x8"], fp8["p8"], None, C2=w["g"], a_row_scale=w["rs"],
-                             b_scale=fp8["scales"][2 * l + 1:2 * l + 2], M=M, N=f, K=d, lda=d, ldb=d, ldc=f,
-                             b_off=o(p + "fc1.weight"), bias=p32, bias_off=o(p + "fc1.bias"), epilogue=EPI_GELU)
-                ops.gemm(w["g"], p16, hin, M=M, N=d, K=f, lda=f, ldb=f, ldc=d, b_off=o(p + "fc2.weight"), bias=p32,
-                         bias_off=o(p + "fc2.bias"), epilogue=EPI_RESIDUAL, R=hmid, ldr=d)
-            else:
-                self._ffn(w, hmid, hin, p, M, d, f)  # result back in `hin`
-        ops.layernorm_fwd(w["h"][cur], st.view("model.encoder.layer_norm.weight"), st.view("model.encoder.layer_norm.bias"),
+        w = self._encoder_ws(B)
+        f8 = self._fp8
+        if f8 is not None and "x8" not in w:
+            w["x8"] = torch.zeros(M * d, dtype=torch.uint8, device=self.device)
+            w["rs"] = torch.zeros(M, dtype=torch.float32, device=self.device)
+
+        def w8(i):  # enable_fp8_encoder's operands of weight matrix i: q|k|v (2l) or fc1 (2l + 1) of layer l
+            return dict(w=(f8["p8"], f8["scales"][i:i + 1], w["x8"], w["rs"])) if f8 is not None else None
+
+        h, hmid = w["h"]
+        self.encoder_stem(x, w, h)
+        for l, (sa, ff) in enumerate(self.enc_blocks):
+            sa.forward(h, hmid, w["sa"], B, T, fp8=w8(2 * l))
+            ff.forward(hmid, h, w["ff"], M, fp8=w8(2 * l + 1))  # result back in `h`
+        ops.layernorm_fwd(h, st.view("model.encoder.layer_norm.weight"), st.view("model.encoder.layer_norm.bias"),
                           w["out"], None, M, d, s.layer_norm_eps)
         return w["out"].view(B, T, d)
 
@@ -349,31 +358,24 @@ class WhisperEngine:
         """Per decoder layer: K|V projections of the encoder states, bf16 [B*1500, 2d] (computed once
         per clip, like the cross-attention cache at $TF/models/whisper/modeling_whisper.py:312-335)."""
         self._await_all()
-        s, st = self.s, self.store
-        d = s.d_model
         B, T, _ = enc.shape
-        out = []
-        for l in range(s.decoder_layers):
-            p = f"model.decoder.layers.{l}.encoder_attn."
-            kv = torch.empty(B * T * 2 * d, dtype=torch.bfloat16, device=self.device)
-            ops.gemm(enc, st.p16, kv, M=B * T, N=2 * d, K=d, lda=d, ldb=d, ldc=2 * d, b_off=st.off(p + "k_proj.weight"),
-                     bias=st.p32, bias_off=st.off(p + "k_proj.bias__zero"))
-            out.append(kv)
-        return out
+        n = B * T * 2 * self.s.d_model
+        return [ca.project_kv(enc, dict(kv=torch.empty(n, dtype=torch.bfloat16, device=self.device)), B, T)
+                for _, ca, _ in self.dec_blocks]
 
     def _decoder_ws(self, B, L):
         key = (B, L)
         if key in self._dec_ws:
             return self._dec_ws[key]
-        s, dev = self.s, self.device
-        d, f, H, Te = s.d_model, s.decoder_ffn_dim, s.decoder_attention_heads, s.max_source_positions
-        Lp, Tep = _r8(L), _r8(Te)
-        z = lambda n, dt=torch.bfloat16: torch.zeros(n, dtype=dt, device=dev)  # noqa: E731
-        w = dict(h=[z(B * L * d), z(B * L * d)], x=z(B * L * d), qkv=z(B * L * 3 * d), q=z(B * L * d), ctx=z(B * L * d),
-                 g=z(B * L * f), hf=z(B * L * d))
+        s = self.s
+        d, H, Te = s.d_model, s.decoder_attention_heads, s.max_source_positions
+        z = zeros_on(self.device)
+        w = dict(h=[z(B * L * d), z(B * L * d)], hf=z(B * L * d))
+        for sa, ca, ff in self.dec_blocks[:1]:  # (every layer's blocks have the same shapes)
+            w.update(sa=sa.alloc(B, L, z, train=False), ca=ca.alloc(B, L, Te, z, train=False), ff=ff.alloc(B * L, z, train=False))
         # one decoded token per clip: the cross-attention may deal a (clip, head)'s 1500 keys to several workgroups
         # (CaAttnDesc.split_ws; it decides by B x H against the CU count)
-        w["split"] = ops.attn_split_workspace(B, H, dev) if L == 1 else None
+        w["split"] = ops.attn_split_workspace(B, H, self.device) if L == 1 else None
         self._dec_ws[key] = w
         return w
 
@@ -381,60 +383,26 @@ class WhisperEngine:
         """Teacher-forced decoder: input_ids [B, L] -> fp32 logits [B, L, V] (or [B, 1, V] for the
         last position only)."""
         self._await_all()
-        s, st = self.s, self.store
-        p32, p16, o = st.p32, st.p16, st.off
-        dev = self.device
+        s, dev = self.s, self.device
         B, L = input_ids.shape
         if L > s.max_target_positions:
             raise ValueError(f"sequence length {L} cannot exceed the maximum allowed length of {s.max_target_positions} tokens")
-        d, f, H, Te = s.d_model, s.decoder_ffn_dim, s.decoder_attention_heads, s.max_source_positions
-        hd = d // H
-        M = B * L
-        Tep = _r8(Te)
+        M, Te = B * L, s.max_source_positions
         w = self._decoder_ws(B, L)
         kv = kv if kv is not None else self.cross_kv(enc)
         ids = input_ids.to(dev, torch.int32).contiguous().view(-1)
         pos = torch.arange(L, dtype=torch.int32, device=dev).repeat(B)
-        ops.embed_tokens(p16[o("model.decoder.embed_tokens.weight"):], p16[o("model.decoder.embed_positions.weight"):],
-                         ids, pos, w["h"][0], M, d)
-        for l in range(s.decoder_layers):
-            p = f"model.decoder.layers.{l}."
-            h0, h1 = w["h"][0], w["h"][1]
-            # causal self-attention
-            ops.layernorm_fwd(h0, st.view(p + "self_attn_layer_norm.weight"), st.view(p + "self_attn_layer_norm.bias"),
-                              w["x"], None, M, d, s.layer_norm_eps)
-            ops.gemm(w["x"], p16, w["qkv"], M=M, N=3 * d, K=d, lda=d, ldb=d, ldc=3 * d,
-                     b_off=o(p + "self_attn.q_proj.weight"), bias=p32, bias_off=o(p + "self_attn.q_proj.bias"))
-            self._self_attention(w["qkv"], w["ctx"], B, L, H, hd, d, causal=True)
-            ops.gemm(w["ctx"], p16, h1, M=M, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(p + "self_attn.out_proj.weight"),
-                     bias=p32, bias_off=o(p + "self_attn.out_proj.bias"), epilogue=EPI_RESIDUAL, R=h0, ldr=d)
-            # cross-attention over the encoder states
-            ops.layernorm_fwd(h1, st.view(p + "encoder_attn_layer_norm.weight"), st.view(p + "encoder_attn_layer_norm.bias"),
-                              w["x"], None, M, d, s.layer_norm_eps)
-            ops.gemm(w["x"], p16, w["q"], M=M, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(p + "encoder_attn.q_proj.weight"),
-                     bias=p32, bias_off=o(p + "encoder_attn.q_proj.bias"))
-            Lqp = (L + 31) // 32 * 32
-            ops.attn_fwd(w["q"], kv[l], kv[l], w["ctx"], self._lse(B * H * Lqp), B=B, H=H, Tq=L, Tk=Te, hd=hd, Tqp=Lqp,
-                         scale=hd ** -0.5, ldq=d, ldk=2 * d, ldv=2 * d, ldo=d, sqb=L * d, skb=Te * 2 * d,
-                         svb=Te * 2 * d, sob=L * d, k_off=0, v_off=d)
-            ops.gemm(w["ctx"], p16, h0, M=M, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(p + "encoder_attn.out_proj.weight"),
-                     bias=p32, bias_off=o(p + "encoder_attn.out_proj.bias"), epilogue=EPI_RESIDUAL, R=h1, ldr=d)
-            # feed-forward (result back in h1, then swap roles by copying the pointer order)
-            self._ffn(w, h0, h1, p, M, d, f)
-            w["h"][0], w["h"][1] = h1, h0
-        ops.layernorm_fwd(w["h"][0], st.view("model.decoder.layer_norm.weight"), st.view("model.decoder.layer_norm.bias"),
-                          w["hf"], None, M, d, s.layer_norm_eps)
-        V = s.vocab_size
-        Vp = _r8(V)
+        h0, h1 = w["h"]
+        self._embed(ids, pos, h0, M)
+        for l, (sa, ca, ff) in enumerate(self.dec_blocks):
+            sa.forward(h0, h1, w["sa"], B, L)
+            ca.forward(h1, h0, w["ca"], B, L, Te, kv=kv[l])
+            ff.forward(h0, h1, w["ff"], M)
+            h0, h1 = h1, h0
+        V, Vp = s.vocab_size, _r8(s.vocab_size)
         if last_only:
-            rows = w["hf"].view(B, L, d)[:, -1, :].contiguous()
-            # (torch.empty: the GEMM writes all V columns, the Vp - V pad columns are never read - no fill kernel per call)
-            logits = torch.empty(B, Vp, dtype=torch.float32, device=dev)
-            ops.gemm(rows, p16, logits, M=B, N=V, K=d, lda=d, ldb=d, ldc=Vp, b_off=o("model.decoder.embed_tokens.weight"))
-            return logits.view(B, 1, Vp)[:, :, :V]
-        logits = torch.empty(M, Vp, dtype=torch.float32, device=dev)
-        ops.gemm(w["hf"], p16, logits, M=M, N=V, K=d, lda=d, ldb=d, ldc=Vp, b_off=o("model.decoder.embed_tokens.weight"))
-        self._last_logits = logits
+            return self._head(h0, w["hf"], M, last_of=B).view(B, 1, Vp)[:, :, :V]
+        logits = self._last_logits = self._head(h0, w["hf"], M)
         return logits.view(B, L, Vp)[:, :, :V]
 
     # ---- incremental decoding (self-attention K|V cache) ----------------------------------------
@@ -460,52 +428,47 @@ class WhisperEngine:
             raise ValueError("decode cache too small / batch mismatch")
         if pos0 > 0 and n != 1:
             raise ValueError("after the first call tokens are appended one at a time")
-        d, f, H, Te = s.d_model, s.decoder_ffn_dim, s.decoder_attention_heads, s.max_source_positions
+        d, H, Te = s.d_model, s.decoder_attention_heads, s.max_source_positions
         hd = d // H
         M = B * n
         w = self._decoder_ws(B, n)
+        x, q, ctx, lse = w["ca"]["x"], w["ca"]["q"], w["ca"]["ctx"], w["ca"]["lse"]
         ids = new_ids.to(dev, torch.int32).contiguous().view(-1)
         pos = (torch.arange(n, dtype=torch.int32, device=dev) + pos0).repeat(B)
-        ops.embed_tokens(p16[o("model.decoder.embed_tokens.weight"):], p16[o("model.decoder.embed_positions.weight"):],
-                         ids, pos, w["h"][0], M, d)
+        h0, h1 = w["h"]
+        self._embed(ids, pos, h0, M)
         Lk = pos0 + n
         nqp = (n + 31) // 32 * 32
-        for l in range(s.decoder_layers):
+        for l, (_, _, ff) in enumerate(self.dec_blocks):
             p = f"model.decoder.layers.{l}."
-            h0, h1 = w["h"][0], w["h"][1]
             ckv = cache["kv"][l]
             ops.layernorm_fwd(h0, st.view(p + "self_attn_layer_norm.weight"), st.view(p + "self_attn_layer_norm.bias"),
-                              w["x"], None, M, d, s.layer_norm_eps)
-            ops.gemm(w["x"], p16, w["q"], M=M, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(p + "self_attn.q_proj.weight"),
+                              x, None, M, d, s.layer_norm_eps)
+            ops.gemm(x, p16, q, M=M, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(p + "self_attn.q_proj.weight"),
                      bias=p32, bias_off=o(p + "self_attn.q_proj.bias"))
             # K|V of the new tokens go straight into the cache rows (batch b, position pos0..)
-            ops.gemm(w["x"], p16, ckv, M=n, N=2 * d, K=d, lda=d, ldb=d, ldc=2 * d, c_off=pos0 * 2 * d,
+            ops.gemm(x, p16, ckv, M=n, N=2 * d, K=d, lda=d, ldb=d, ldc=2 * d, c_off=pos0 * 2 * d,
                      b_off=o(p + "self_attn.k_proj.weight"), bias=p32, bias_off=o(p + "self_attn.k_proj.bias__zero"),
                      batch2=B, sA=(0, n * d), sC=(0, Lmax * 2 * d))
-            ops.attn_fwd(w["q"], ckv, ckv, w["ctx"], self._lse(B * H * nqp), B=B, H=H, Tq=n, Tk=Lk, hd=hd, Tqp=nqp,
+            ops.attn_fwd(q, ckv, ckv, ctx, lse, B=B, H=H, Tq=n, Tk=Lk, hd=hd, Tqp=nqp,
                          scale=hd ** -0.5, ldq=d, ldk=2 * d, ldv=2 * d, ldo=d, sqb=n * d, skb=Lmax * 2 * d,
                          svb=Lmax * 2 * d, sob=n * d, k_off=0, v_off=d, causal=(n > 1))
-            ops.gemm(w["ctx"], p16, h1, M=M, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(p + "self_attn.out_proj.weight"),
+            ops.gemm(ctx, p16, h1, M=M, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(p + "self_attn.out_proj.weight"),
                      bias=p32, bias_off=o(p + "self_attn.out_proj.bias"), epilogue=EPI_RESIDUAL, R=h0, ldr=d)
             ops.layernorm_fwd(h1, st.view(p + "encoder_attn_layer_norm.weight"), st.view(p + "encoder_attn_layer_norm.bias"),
-                              w["x"], None, M, d, s.layer_norm_eps)
-            ops.gemm(w["x"], p16, w["q"], M=M, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(p + "encoder_attn.q_proj.weight"),
+                              x, None, M, d, s.layer_norm_eps)
+            ops.gemm(x, p16, q, M=M, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(p + "encoder_attn.q_proj.weight"),
                      bias=p32, bias_off=o(p + "encoder_attn.q_proj.bias"))
-            ops.attn_fwd(w["q"], cross_kv[l], cross_kv[l], w["ctx"], self._lse(B * H * nqp), B=B, H=H, Tq=n, Tk=Te, hd=hd,
+            ops.attn_fwd(q, cross_kv[l], cross_kv[l], ctx, lse, B=B, H=H, Tq=n, Tk=Te, hd=hd,
                          Tqp=nqp, scale=hd ** -0.5, ldq=d, ldk=2 * d, ldv=2 * d, ldo=d, sqb=n * d, skb=Te * 2 * d,
                          svb=Te * 2 * d, sob=n * d, k_off=0, v_off=d)
-            ops.gemm(w["ctx"], p16, h0, M=M, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(p + "encoder_attn.out_proj.weight"),
+            ops.gemm(ctx, p16, h0, M=M, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(p + "encoder_attn.out_proj.weight"),
                      bias=p32, bias_off=o(p + "encoder_attn.out_proj.bias"), epilogue=EPI_RESIDUAL, R=h1, ldr=d)
-            self._ffn(w, h0, h1, p, M, d, f)
-            w["h"][0], w["h"][1] = h1, h0
-        ops.layernorm_fwd(w["h"][0], st.view("model.decoder.layer_norm.weight"), st.view("model.decoder.layer_norm.bias"),
-                          w["hf"], None, M, d, s.layer_norm_eps)
-        V, Vp = s.vocab_size, _r8(s.vocab_size)
-        rows = w["hf"].view(B, n, d)[:, -1, :].contiguous()
-        logits = torch.empty(B, Vp, dtype=torch.float32, device=dev)
-        ops.gemm(rows, p16, logits, M=B, N=V, K=d, lda=d, ldb=d, ldc=Vp, b_off=o("model.decoder.embed_tokens.weight"))
+            ff.forward(h0, h1, w["ff"], M)
+            h0, h1 = h1, h0
+        logits = self._head(h0, w["hf"], M, last_of=B)
         cache["pos"] = Lk
-        return logits[:, :V]
+        return logits[:, :s.vocab_size]
 
     # ---- one-token step with static shapes and pointers (capturable in a HIP graph) -----------------
     def _graph_state(self, cache: dict, cross_kv: list, pad_id: int, eos_id: int):
@@ -596,11 +559,10 @@ class WhisperEngine:
         s, st = self.s, self.store
         p32, p16, o = st.p32, st.p16, st.off
         B, Lmax = cache["B"], cache["max_len"]
-        d, f, H, Te = s.d_model, s.decoder_ffn_dim, s.decoder_attention_heads, s.max_source_positions
+        d, H, Te = s.d_model, s.decoder_attention_heads, s.max_source_positions
         hd = d // H
         w = self._decoder_ws(B, 1)
-        import os
-
+        x, q, ctx, lse = w["ca"]["x"], w["ca"]["q"], w["ca"]["ctx"], w["ca"]["lse"]
         # LayerNorm + query projection inside the cross-attention launch: every (clip, head) workgroup streams its head's
         # 64 x d slice of Wq in its prologue (128 KB at d = 1024, a third of the K|V it then streams) - worth it while the
         # launch is short of workgroups (32 clips x 16 heads = 2 per CU: 3.05 against 3.14 ms per token), not above (64
@@ -608,36 +570,35 @@ class WhisperEngine:
         fz = os.environ.get("CA_DECODE_FUSED")
         ncu = torch.cuda.get_device_properties(self.device).multi_processor_count
         fused = (fz != "0" if fz is not None else B * H <= 2 * ncu) and hd <= 64 and d <= 2048
-        ops.embed_tokens(p16[o("model.decoder.embed_tokens.weight"):], p16[o("model.decoder.embed_positions.weight"):],
-                         g["tok"], g["pos"], w["h"][0], B, d)
-        h0, h1 = w["h"][0], w["h"][1]
-        for l in range(s.decoder_layers):
+        h0, h1 = w["h"]
+        self._embed(g["tok"], g["pos"], h0, B)
+        for l, (_, _, ff) in enumerate(self.dec_blocks):
             p = f"model.decoder.layers.{l}."
             ckv = cache["kv"][l]
             ln_in = LN_IN_GEMM and B <= 128 and d <= 2048
             if not ln_in:
                 ops.layernorm_fwd(h0, st.view(p + "self_attn_layer_norm.weight"), st.view(p + "self_attn_layer_norm.bias"),
-                                  w["x"], None, B, d, s.layer_norm_eps)
+                                  x, None, B, d, s.layer_norm_eps)
             # q and the new K|V rows from one launch over the adjacent q|k|v weights: q to its buffer, K|V straight
             # into the cache at the device-side position (CaGemmDesc.c_split_n / c_row_index: the position is data,
             # not a launch argument, so the launch sequence can be replayed as a graph); the LayerNorm in front of it
             # in the same launch's prologue (CaGemmDesc.a_ln_gamma)
-            ops.gemm(h0 if ln_in else w["x"], p16, w["q"], M=B, N=3 * d, K=d, lda=d, ldb=d, ldc=d,
+            ops.gemm(h0 if ln_in else x, p16, q, M=B, N=3 * d, K=d, lda=d, ldb=d, ldc=d,
                      b_off=o(p + "self_attn.q_proj.weight"),
                      bias=p32, bias_off=o(p + "self_attn.q_proj.bias"), c_split_n=d, C_hi=ckv, ldc_hi=2 * d,
                      c_row_index=g["pos"], c_row_mul=Lmax,
                      a_ln=(st.view(p + "self_attn_layer_norm.weight"), st.view(p + "self_attn_layer_norm.bias"),
                            s.layer_norm_eps) if ln_in else None)
-            ops.attn_fwd(w["q"], ckv, ckv, w["ctx"], self._lse(B * H * 32), B=B, H=H, Tq=1, Tk=Lmax, hd=hd, Tqp=32,
+            ops.attn_fwd(q, ckv, ckv, ctx, lse, B=B, H=H, Tq=1, Tk=Lmax, hd=hd, Tqp=32,
                          scale=hd ** -0.5, ldq=d, ldk=2 * d, ldv=2 * d, ldo=d, sqb=d, skb=Lmax * 2 * d,
                          svb=Lmax * 2 * d, sob=d, k_off=0, v_off=d, klen=g["klen"])
-            ops.gemm(w["ctx"], p16, h1, M=B, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(p + "self_attn.out_proj.weight"),
+            ops.gemm(ctx, p16, h1, M=B, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(p + "self_attn.out_proj.weight"),
                      bias=p32, bias_off=o(p + "self_attn.out_proj.bias"), epilogue=EPI_RESIDUAL, R=h0, ldr=d)
             if fused:
                 # LayerNorm + query projection + attention over the cached encoder K|V: one launch (bit-identical to
                 # the three below; CA_DECODE_FUSED=0 keeps them)
                 ops.decode_attn_qproj(h1, st.view(p + "encoder_attn_layer_norm.weight"), st.view(p + "encoder_attn_layer_norm.bias"),
-                                      p16, p32, g["cross"][l], g["cross"][l], w["ctx"], d_model=d, eps=s.layer_norm_eps,
+                                      p16, p32, g["cross"][l], g["cross"][l], ctx, d_model=d, eps=s.layer_norm_eps,
                                       ldx=d, ldw=d, w_off=o(p + "encoder_attn.q_proj.weight"),
                                       bias_off=o(p + "encoder_attn.q_proj.bias"), B=B, H=H, Tk=Te, hd=hd,
                                       scale=hd ** -0.5, ldk=2 * d, ldv=2 * d, ldo=d, skb=Te * 2 * d, svb=Te * 2 * d,
@@ -645,22 +606,20 @@ class WhisperEngine:
             else:
                 if not ln_in:
                     ops.layernorm_fwd(h1, st.view(p + "encoder_attn_layer_norm.weight"), st.view(p + "encoder_attn_layer_norm.bias"),
-                                      w["x"], None, B, d, s.layer_norm_eps)
-                ops.gemm(h1 if ln_in else w["x"], p16, w["q"], M=B, N=d, K=d, lda=d, ldb=d, ldc=d,
+                                      x, None, B, d, s.layer_norm_eps)
+                ops.gemm(h1 if ln_in else x, p16, q, M=B, N=d, K=d, lda=d, ldb=d, ldc=d,
                          b_off=o(p + "encoder_attn.q_proj.weight"), bias=p32, bias_off=o(p + "encoder_attn.q_proj.bias"),
                          a_ln=(st.view(p + "encoder_attn_layer_norm.weight"), st.view(p + "encoder_attn_layer_norm.bias"),
                                s.layer_norm_eps) if ln_in else None)
-                ops.attn_fwd(w["q"], g["cross"][l], g["cross"][l], w["ctx"], self._lse(B * H * 32), B=B, H=H, Tq=1, Tk=Te,
+                ops.attn_fwd(q, g["cross"][l], g["cross"][l], ctx, lse, B=B, H=H, Tq=1, Tk=Te,
                              hd=hd, Tqp=32, scale=hd ** -0.5, ldq=d, ldk=2 * d, ldv=2 * d, ldo=d, sqb=d, skb=Te * 2 * d,
                              svb=Te * 2 * d, sob=d, k_off=0, v_off=d, split_ws=w["split"])
-            ops.gemm(w["ctx"], p16, h0, M=B, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(p + "encoder_attn.out_proj.weight"),
+            ops.gemm(ctx, p16, h0, M=B, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(p + "encoder_attn.out_proj.weight"),
                      bias=p32, bias_off=o(p + "encoder_attn.out_proj.bias"), epilogue=EPI_RESIDUAL, R=h1, ldr=d)
-            self._ffn(w, h0, h1, p, B, d, f)
+            ff.forward(h0, h1, w["ff"], B)
             h0, h1 = h1, h0
-        ops.layernorm_fwd(h0, st.view("model.decoder.layer_norm.weight"), st.view("model.decoder.layer_norm.bias"),
-                          w["hf"], None, B, d, s.layer_norm_eps)
+        self._head(h0, w["hf"], B, logits=g["logits"])
         V, Vp = s.vocab_size, _r8(s.vocab_size)
-        ops.gemm(w["hf"], p16, g["logits"], M=B, N=V, K=d, lda=d, ldb=d, ldc=Vp, b_off=o("model.decoder.embed_tokens.weight"))
         # argmax + the step's bookkeeping in one launch: out[b, pos + 1] = the token (pad for finished rows), done |= eos,
         # tok = the token, pos += 1, klen += 1
         ops.argmax_advance(g["logits"], suppress, g["nxt"], B, V, Vp, g["done"], g["out"], g["tok"], g["pos"], g["klen"],
@@ -674,11 +633,7 @@ class WhisperEngine:
         if decoder_input_ids is None:
             if labels is None:
                 raise ValueError("either labels or decoder_input_ids is required")
-            lab = labels.to(torch.int64)
-            dec = lab.new_zeros(lab.shape)
-            dec[:, 1:] = lab[:, :-1]
-            dec[:, 0] = s.decoder_start_token_id
-            decoder_input_ids = dec.masked_fill(dec == -100, s.pad_token_id)
+            decoder_input_ids = shift_tokens_right(labels, s.pad_token_id, s.decoder_start_token_id)
         logits = self.decode(decoder_input_ids, enc)
         out = dict(logits=logits, loss=None, encoder_last_hidden_state=enc)
         if labels is not None:

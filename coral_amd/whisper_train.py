@@ -18,10 +18,10 @@ import torch
 
 from . import ops
 from .staging import PinnedStager
-from .blocks import CrossAttnBlock, FFNBlock, Scratch, SelfAttnBlock, _z, encoder_backward, norm_plan, wgrad_stream, zeros_on
-from .ops import EPI_GELU, EPI_GELU_RESIDUAL, MNMAJOR
+from .blocks import Scratch, _z, encoder_backward, norm_plan, wgrad_stream, zeros_on
+from .ops import MNMAJOR
 from .wav2vec2 import _r8
-from .whisper import WhisperEngine, WhisperShape
+from .whisper import WhisperEngine, WhisperShape, shift_tokens_right
 
 
 class WhisperTrainEngine(WhisperEngine):
@@ -40,31 +40,11 @@ class WhisperTrainEngine(WhisperEngine):
         self.attention_dropout = attention_dropout
         self._stager = PinnedStager(self.device)
         self.freeze_base = freeze_base
-        s, st = shape, self.store
-        d, eps = s.d_model, s.layer_norm_eps
         self.activation_dropout = activation_dropout
         self.training = True
         self.step_seed = 0
-        self.enc_blocks, self.dec_blocks = [], []
-        for l in range(s.encoder_layers):
-            p = f"model.encoder.layers.{l}."
-            self.enc_blocks.append((
-                SelfAttnBlock(st, p + "self_attn_layer_norm", p + "self_attn.", s.encoder_attention_heads, d, eps, False,
-                              p + "self_attn.q_proj.bias"),
-                FFNBlock(st, p + "final_layer_norm", p + "fc1", p + "fc2", d, s.encoder_ffn_dim, eps)))
-        for l in range(s.decoder_layers):
-            p = f"model.decoder.layers.{l}."
-            self.dec_blocks.append((
-                SelfAttnBlock(st, p + "self_attn_layer_norm", p + "self_attn.", s.decoder_attention_heads, d, eps, True,
-                              p + "self_attn.q_proj.bias"),
-                CrossAttnBlock(st, p + "encoder_attn_layer_norm", p + "encoder_attn.", s.decoder_attention_heads, d, eps),
-                FFNBlock(st, p + "final_layer_norm", p + "fc1", p + "fc2", d, s.decoder_ffn_dim, eps)))
-            # a decoder layer's bias vector (whisper_param_list): self q|k|v, self out, cross q, cross k|v, cross out, fc1, fc2
-            sa, ca, ff = self.dec_blocks[-1]
-            sa.cs_qkv, sa.cs_o, ca.cs, ff.cs_fc1, ff.cs_fc2 = 0, 3 * d, (4 * d, 7 * d), 8 * d, 8 * d + s.decoder_ffn_dim
         self._tw = None
         self._tw_key = None
-        self.zero_mel = torch.zeros(s.num_mel_bins, dtype=torch.bfloat16, device=self.device)
 
     # ---- fp8 forward projections (BASELINE.json configs[4]) ------------------------------------------
     _fp8_train = None
@@ -94,9 +74,6 @@ class WhisperTrainEngine(WhisperEngine):
         self.background_optimizer = not on
         if not on:
             self._fp8_train = None
-            for sa, ff in self.enc_blocks:
-                sa.fp8 = ff.fp8 = None
-                sa.fp8_bwd = ff.fp8_bwd = None
             return
         st, dev, L = self.store, self.device, self.s.encoder_layers
         if ffn2 is None:
@@ -118,7 +95,7 @@ class WhisperTrainEngine(WhisperEngine):
         f8["scale"][nw:] = 448.0 / 16.0
         f8["inv"][nw:] = 16.0 / 448.0
         self._fp8_train = f8
-        self._tw_key = None  # the workspace hands the blocks their staging buffers
+        self._tw_key = None  # the workspace builds the blocks' fp8 operands (_train_ws)
         self.refresh_fp8()                                   # (scale 1: measures every matrix's amax)
         ops.fp8_amax_rotate(f8["amax"], f8["scale"], f8["inv"], nw, margin=1.0)
         self.refresh_fp8()                                   # the real copies
@@ -296,7 +273,7 @@ class WhisperTrainEngine(WhisperEngine):
             enc_sv=[(sa.alloc(B, T, z), ff.alloc(Me, z)) for sa, ff in self.enc_blocks],
             dh=[_z(Md * d, dev) for _ in range(3 * s.decoder_layers + 1)], dec_out=_z(Md * d, dev),
             dec_st=_z(Md * 2, dev, f32),
-            dec_sv=[(sa.alloc(B, L, z), ca.alloc(B, L, T, dev), ff.alloc(Md, z)) for sa, ca, ff in self.dec_blocks],
+            dec_sv=[(sa.alloc(B, L, z), ca.alloc(B, L, T, z), ff.alloc(Md, z)) for sa, ca, ff in self.dec_blocks],
             logits=_z(Md * _r8(s.vocab_size), dev, f32), dlogits=_z(Md * _r8(s.vocab_size), dev, f32),
             dlogits16=_z(Md * _r8(s.vocab_size), dev),
             loss_cnt=_z(2, dev, f32),  # loss_sum (fp32) | count (int32) in adjacent words: cleared by one launch
@@ -328,23 +305,23 @@ class WhisperTrainEngine(WhisperEngine):
             def act(i, buf, w):  # (e4m3 activation, its scale / dequantisation factor / amax accumulator, the weight's factor)
                 return (buf, f8["scale"][nw + i:nw + i + 1], f8["inv"][nw + i:nw + i + 1], f8["amax"][(nw + i) * S:], f8["inv"][w:w + 1])
 
-            for l, (sa, ff) in enumerate(self.enc_blocks):
-                sa.fp8 = (f8["p8"], f8["inv"][4 * l:4 * l + 1], f8["x8"], f8["rs"])
-                ff.fp8 = (f8["p8"], f8["inv"][4 * l + 2:4 * l + 3], f8["x8"], f8["rs"])
-                ff.fp8_fc2 = act(2 * l, f8["g8"], 4 * l + 3) if f8["ffn2"] else None       # fc2 <- GELU output
-                sa.fp8_out = act(2 * l + 1, f8["c8"], 4 * l + 1) if f8["out8"] else None  # out_proj <- attention output
-                ff.fp8_du = None
+            # per encoder layer the (attention, feed-forward) blocks' fp8 operands (blocks.py), passed by forward_train
+            f8["blocks"] = []
+            for l in range(s.encoder_layers):
+                a8 = dict(w=(f8["p8"], f8["inv"][4 * l:4 * l + 1], f8["x8"], f8["rs"]),
+                          out=act(2 * l + 1, f8["c8"], 4 * l + 1) if f8["out8"] else None)  # out_proj <- attention output
+                m8 = dict(w=(f8["p8"], f8["inv"][4 * l + 2:4 * l + 3], f8["x8"], f8["rs"]),
+                          fc2=act(2 * l, f8["g8"], 4 * l + 3) if f8["ffn2"] else None)     # fc2 <- GELU output
                 if f8["dgrad"]:  # (transposed weights, offset, e4m3 dY, its row scales, the weight's dequantisation factor)
                     fd, dd = s.encoder_ffn_dim * s.d_model, s.d_model * s.d_model
                     base = l * (2 * fd + dd)
-                    ff.fp8_bwd = (f8["p8t"], base, f8["dy8"], f8["drs"], f8["inv"][4 * l + 3:4 * l + 4])
-                    sa.fp8_bwd = (f8["p8t"], base + fd, f8["dy8"], f8["drs"], f8["inv"][4 * l + 1:4 * l + 2])
+                    m8["bwd"] = (f8["p8t"], base, f8["dy8"], f8["drs"], f8["inv"][4 * l + 3:4 * l + 4])
+                    a8["bwd"] = (f8["p8t"], base + fd, f8["dy8"], f8["drs"], f8["inv"][4 * l + 1:4 * l + 2])
                     if f8["dgrad_fc1"]:
-                        i = nw + 2 * len(self.enc_blocks) + l
-                        ff.fp8_du = dict(buf=f8["du8"], scale=f8["scale"][i:i + 1], inv=f8["inv"][i:i + 1], amax=f8["amax"][i * S:],
-                                         inv_w=f8["inv"][4 * l + 2:4 * l + 3], w_off=base + fd + dd, ready=f8["du_ready"])
-                else:
-                    ff.fp8_bwd = sa.fp8_bwd = None
+                        i = nw + 2 * s.encoder_layers + l
+                        m8["du"] = dict(buf=f8["du8"], scale=f8["scale"][i:i + 1], inv=f8["inv"][i:i + 1], amax=f8["amax"][i * S:],
+                                        inv_w=f8["inv"][4 * l + 2:4 * l + 3], w_off=base + fd + dd, ready=f8["du_ready"])
+                f8["blocks"].append((a8, m8))
         self._tw, self._tw_key = w, key
         return w
 
@@ -354,7 +331,6 @@ class WhisperTrainEngine(WhisperEngine):
         LayerDrop decisions (one bool per layer, $TF/models/whisper/modeling_whisper.py:626-634,771-779);
         a dropped layer is the identity in forward and backward."""
         s, st = self.s, self.store
-        p32, p16, o = st.p32, st.p16, st.off
         dev = self.device
         x = self._stager.to_device(input_features, torch.float32, "x")  # pinned staging: no host stall (staging.py)
         B, mels, Tin = x.shape
@@ -365,10 +341,7 @@ class WhisperTrainEngine(WhisperEngine):
         L = lab.shape[1]
         if L > s.max_target_positions:
             raise ValueError(f"Labels' sequence length {L} cannot exceed the maximum allowed length of {s.max_target_positions} tokens.")
-        dec_in = lab.new_zeros(lab.shape)
-        dec_in[:, 1:] = lab[:, :-1]
-        dec_in[:, 0] = s.decoder_start_token_id
-        dec_in = dec_in.masked_fill(dec_in == -100, s.pad_token_id)
+        dec_in = shift_tokens_right(lab, s.pad_token_id, s.decoder_start_token_id)
         w = self._train_ws(B, L)
         Me, Md = B * T, B * L
         drop = self.activation_dropout if self.training else 0.0
@@ -385,31 +358,22 @@ class WhisperTrainEngine(WhisperEngine):
         mask_time_d = self._stager.to_device(mask_time, torch.uint8, "tm") if mask_time is not None else None
         mask_feature_d = self._stager.to_device(mask_feature, torch.uint8, "fm") if mask_feature is not None else None
         self._await("front")
-        # encoder stem
-        for b in range(B):
-            ops.transpose_f32_bf16(x[b], w["xin"][(b * (Tin + 2) + 1) * mels:], mels, Tin)
-            if mask_time is not None or mask_feature is not None:  # SpecAugment on the input features
-                tm = mask_time_d[b:b + 1].contiguous() if mask_time_d is not None else None
-                fm = mask_feature_d[b:b + 1].contiguous() if mask_feature_d is not None else None
-                ops.mask_frames(w["xin"][(b * (Tin + 2) + 1) * mels:], tm, fm, self.zero_mel, None, 1, Tin, mels)
-        ops.gemm(w["xin"], self.conv1_wr, w["pre1"], C2=w["c1"], c_off=d, c2_off=d, M=Tin, N=d, K=3 * mels, lda=mels,
-                 ldb=3 * mels, ldc=d, bias=p32, bias_off=o("model.encoder.conv1.bias"), epilogue=EPI_GELU, batch2=B,
-                 sA=(0, (Tin + 2) * mels), sC=(0, (Tin + 2) * d))
-        ops.gemm(w["c1"], self.conv2_wr, w["pre2"], C2=w["eh"][0], M=T, N=d, K=3 * d, lda=2 * d, ldb=3 * d, ldc=d, bias=p32,
-                 bias_off=o("model.encoder.conv2.bias"), epilogue=EPI_GELU_RESIDUAL, R=p16, r_off=o("model.encoder.embed_positions.weight"),
-                 ldr=d, batch2=B, sA=(0, (Tin + 2) * d), sC=(0, T * d), sR=(0, 0))
+        self.encoder_stem(x, w, w["eh"][0], pre=(w["pre1"], w["pre2"]), mask_time=mask_time_d, mask_feature=mask_feature_d)
         if hp > 0.0:
             ops.dropout(w["eh"][0], w["eh"][0], Me * d, *hd(1000))
         ek = [True] * s.encoder_layers if enc_keep is None else [bool(k) for k in enc_keep]
         dk = [True] * s.decoder_layers if dec_keep is None else [bool(k) for k in dec_keep]
+        f8 = self._fp8_train
         for l, (sa, ff) in enumerate(self.enc_blocks):
             self._await(f"enc{l}")
             if not ek[l]:
                 w["eh"][2 * l + 2].copy_(w["eh"][2 * l])
                 continue
             sv_a, sv_f = w["enc_sv"][l]
-            sa.forward(w["eh"][2 * l], w["eh"][2 * l + 1], sv_a, B, T, hdrop=hd(256 + l), adrop=ad(768 + l))
-            ff.forward(w["eh"][2 * l + 1], w["eh"][2 * l + 2], sv_f, Me, drop, self.step_seed * 4096 + l, hdrop=hd(512 + l))
+            a8, m8 = f8["blocks"][l] if f8 is not None else (None, None)
+            sa.forward(w["eh"][2 * l], w["eh"][2 * l + 1], sv_a, B, T, hdrop=hd(256 + l), adrop=ad(768 + l), fp8=a8)
+            ff.forward(w["eh"][2 * l + 1], w["eh"][2 * l + 2], sv_f, Me, drop, self.step_seed * 4096 + l, hdrop=hd(512 + l),
+                       fp8=m8)
         self._await("encf")
         self._await("emb")
         ops.layernorm_fwd(w["eh"][-1], st.view("model.encoder.layer_norm.weight"), st.view("model.encoder.layer_norm.bias"),
@@ -417,8 +381,7 @@ class WhisperTrainEngine(WhisperEngine):
         # decoder
         ids = self._stager.to_device(dec_in, torch.int32, "ids").view(-1)
         pos = torch.arange(L, dtype=torch.int32, device=dev).repeat(B)
-        ops.embed_tokens(p16[o("model.decoder.embed_tokens.weight"):], p16[o("model.decoder.embed_positions.weight"):],
-                         ids, pos, w["dh"][0], Md, d)
+        self._embed(ids, pos, w["dh"][0], Md)
         if hp > 0.0:
             ops.dropout(w["dh"][0], w["dh"][0], Md * d, *hd(3000))
         for l, (sa, ca, ff) in enumerate(self.dec_blocks):
@@ -433,10 +396,8 @@ class WhisperTrainEngine(WhisperEngine):
             ff.forward(w["dh"][3 * l + 2], w["dh"][3 * l + 3], sv_f, Md, drop, self.step_seed * 4096 + 2048 + l,
                        hdrop=hd(2816 + l))
         self._await_all()  # decf and anything not waited for above
-        ops.layernorm_fwd(w["dh"][-1], st.view("model.decoder.layer_norm.weight"), st.view("model.decoder.layer_norm.bias"),
-                          w["dec_out"], w["dec_st"], Md, d, s.layer_norm_eps)
+        self._head(w["dh"][-1], w["dec_out"], Md, logits=w["logits"], stats=w["dec_st"])
         V, Vp = s.vocab_size, _r8(s.vocab_size)
-        ops.gemm(w["dec_out"], p16, w["logits"], M=Md, N=V, K=d, lda=d, ldb=d, ldc=Vp, b_off=o("model.decoder.embed_tokens.weight"))
         ops.clear_ranges(w["loss_cnt"], ((0, 2),))  # loss_sum | count (adjacent 4-byte words): one launch
         w["loss_sum"], w["count"] = w["loss_cnt"][0:1], w["loss_cnt"][1:2].view(torch.int32)
         lab32 = self._stager.to_device(lab, torch.int32, "lab").view(-1)

@@ -84,6 +84,42 @@ def test_whisper_forward_loss_and_greedy_vs_oracle(golden_dir):
     check_greedy_rows(rows, ids, want, len(prefix), accept=2e-2, forced=5e-2, label="whisper_tiny")
 
 
+def test_whisper_inference_forward_is_the_training_forward_bit_for_bit():
+    """encode() / decode() run the pre-LN blocks on inference workspaces (no saved states; at M <= 128 rows the FFN's
+    LayerNorm inside fc1's prologue), forward_train() on training ones: with every dropout at 0 they give the same
+    encoder states and logits bit for bit.  The two fp8 switches stay apart: enable_fp8_encoder() leaves forward_train()
+    as it is, enable_fp8_forward() leaves encode() as it is."""
+    from coral_amd.whisper import WhisperShape, shift_tokens_right
+    from coral_amd.whisper_train import WhisperTrainEngine
+    from oracle import whisper_ref as w
+
+    kw, c = _tiny()
+    eng = WhisperTrainEngine(WhisperShape(**kw), DEV).eval()
+    eng.load_state_dict(w.synth_params(c))
+    g = torch.Generator().manual_seed(21)
+    feats = torch.randn(2, 80, 3000, generator=g) * 0.5
+    labels = torch.randint(0, 150, (2, 9), generator=g)
+    labels[1, 6:] = -100
+
+    def train_forward():
+        out = eng.forward_train(feats, labels)
+        return eng._saved["w"]["enc_out"].view(2, -1, kw["d_model"]).clone(), out["logits"].clone()
+
+    enc_t, logits_t = train_forward()
+    enc = eng.encode(feats)
+    assert torch.equal(enc, enc_t)
+    assert torch.equal(eng.decode(shift_tokens_right(labels, c.pad_token_id, c.decoder_start_token_id), enc), logits_t)
+    bf16 = enc.clone()
+    eng.enable_fp8_encoder()
+    enc8 = eng.encode(feats).clone()
+    assert not torch.equal(enc8, bf16)  # (the fp8 encoder really ran)
+    enc_t2, logits_t2 = train_forward()
+    assert torch.equal(enc_t2, enc_t) and torch.equal(logits_t2, logits_t)
+    eng.enable_fp8_encoder(False)
+    eng.enable_fp8_forward()
+    assert torch.equal(eng.encode(feats), bf16)
+
+
 def test_whisper_medium_shape_smoke():
     """Real head count / dims of whisper-medium on one clip, two layers each (shape plumbing)."""
     from coral_amd.whisper import CORAL_WHISPER_SHAPES, WhisperEngine, WhisperShape

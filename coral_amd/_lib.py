@@ -135,6 +135,22 @@ class CaFp8RefreshTask(C.Structure):
                 + [("rows", C.c_int32), ("cols", C.c_int32)])
 
 
+class CaCtcBeamDesc(C.Structure):
+    """Mirror of `CaCtcBeamDesc` in include/coral_amd.h."""
+
+    _fields_ = [("logits", C.c_void_p), ("ldv", C.c_int64), ("in_len", C.c_void_p),
+                ("B", C.c_int32), ("T", C.c_int32), ("V", C.c_int32), ("blank", C.c_int32), ("delimiter", C.c_int32),
+                ("forbidden", C.c_void_p), ("pfx_keys", C.c_void_p), ("pfx_wid", C.c_void_p), ("n_pfx", C.c_int64),
+                ("ng_keys", C.c_void_p), ("ng_logp", C.c_void_p), ("ng_backoff", C.c_void_p),
+                ("ng_count", C.c_int64 * 5),
+                ("order", C.c_int32), ("bos_wid", C.c_int32), ("eos_wid", C.c_int32), ("unk_wid", C.c_int32),
+                ("beam_width", C.c_int32),
+                ("alpha", C.c_float), ("beta", C.c_float), ("unk_score_offset", C.c_float),
+                ("token_min_logp", C.c_float), ("beam_prune_logp", C.c_float), ("score_boundary", C.c_int32),
+                ("ids_out", C.c_void_p), ("out_len", C.c_void_p), ("score_out", C.c_void_p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
+
+
 FP8_GROUP_MAX = 8  # CA_FP8_GROUP_MAX
 KMAJOR, MNMAJOR = 0, 1
 EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_DGELU, EPI_GELU_RESIDUAL = 0, 1, 2, 3, 4
@@ -213,6 +229,8 @@ SIGNATURES = {
         C.c_int,
         [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _vp],
     ),
+    "ca_ctc_beam_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "ca_ctc_beam_decode": (C.c_int, [C.POINTER(CaCtcBeamDesc), _vp]),
     "ca_mask_frames": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "ca_regroup_pad": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "ca_posconv_partial_floats": (_i64, [_i32]),

@@ -1,5 +1,6 @@
 """`evaluate(config)` — mirror of R/src/coral/evaluate.py:29-85: load the saved model + processor (wav2vec2 or
-Whisper, by the saved architecture), transcribe the evaluation examples in batches (greedy CTC, or log-mel +
+Whisper, by the saved architecture), transcribe the evaluation examples in batches (greedy CTC - or the LM-fused CTC
+beam search when the model directory holds `language_model/*.arpa` and `no_lm` is false -, or log-mel +
 greedy `generate(language="danish", task="transcribe")`, on the GPU), normalise both sides like the reference
 (lower / strip) and report CER / WER.  The demographic slicing of the
 reference (`get_score_df`, :161-216) is pandas reporting and out of scope."""
@@ -29,7 +30,11 @@ def transcribe(model, processor, arrays: list, batch_size: int = 16) -> list[str
         batch = processor.feature_extractor.pad(feats, padding="longest")
         with torch.no_grad():
             model(torch.from_numpy(batch["input_values"]), torch.from_numpy(batch["attention_mask"]))
-        ids, _ = model.engine.greedy_decode()
+        if getattr(processor, "lm", None) is not None:  # Wav2Vec2ProcessorWithLM: LM-fused beam search on the GPU
+            ids, _ = model.engine.beam_decode(processor.device_tables(model.engine.device), tokenizer=processor.tokenizer,
+                                              **processor.decoder_params)
+        else:
+            ids, _ = model.engine.greedy_decode()
         out += [processor.tokenizer.decode(r, group_tokens=False) for r in ids]
     return out
 
@@ -76,7 +81,9 @@ def evaluate(config, examples: list | None = None) -> dict:
     mcfg = DictConfig(model=DictConfig(type=mtype, sampling_rate=config.sampling_rate, decoder=None),
                       model_dir=model_dir, padding="longest",
                       max_seconds_per_example=config.max_seconds_per_example)
-    saved = load_model_setup(mcfg).load_saved()
+    setup = load_model_setup(mcfg)
+    # `no_lm` (R/src/coral/evaluate.py:123-158): false decodes with model_dir/language_model/ when there is one
+    saved = setup.load_saved() if mtype == "whisper" else setup.load_saved(no_lm=bool(config.get("no_lm", False)))
     model, processor = saved.model, saved.processor
     id_rows = None
     if mtype == "whisper":

@@ -193,14 +193,25 @@ class Wav2Vec2ModelSetup(ModelSetup):
     def load_training_arguments(self) -> TrainingArgs:
         return _training_args(self.config, self.config.model.learning_rate)
 
-    def load_saved(self) -> PreTrainedModelData:
+    def load_saved(self, no_lm: bool = False) -> PreTrainedModelData:
+        """The saved model and its processor.  With `model_dir/language_model/*.arpa` present and `no_lm` false the
+        processor is a `Wav2Vec2ProcessorWithLM` (R/src/coral/evaluate.py:123-158); a directory holding only a KenLM
+        `.bin` decodes greedily, with one warning."""
         from .modeling import Wav2Vec2ForCTC
+        from .ngram import find_language_model
+        from .processor import Wav2Vec2ProcessorWithLM
 
         model_dir = Path(self.config.model_dir)
         if not model_dir.exists():
             raise FileNotFoundError(f"{model_dir} does not exist (no hub access in this environment)")
         tokenizer = CTCTokenizer.from_pretrained(model_dir)
         processor = Wav2Vec2Processor(WaveformFeatureExtractor(self.config.model.sampling_rate), tokenizer)
+        arpa, has_bin = (None, False) if no_lm else find_language_model(model_dir)
+        if arpa is not None:
+            processor = Wav2Vec2ProcessorWithLM.from_pretrained(model_dir, self.config.model.sampling_rate)
+        elif has_bin:
+            logger.warning("%s/language_model holds a KenLM binary only, which cannot be read without KenLM: decoding "
+                           "without the language model. Store the ARPA text file (`3gram.arpa`) there to use it.", model_dir)
         model = Wav2Vec2ForCTC.from_pretrained(str(model_dir))
         collator = DataCollatorCTCWithPadding(processor=processor, sample_rate=self.config.model.sampling_rate,
                                               max_seconds_per_example=self.config.max_seconds_per_example,

@@ -532,6 +532,35 @@ def ctc_greedy_decode(logits, in_len, raw, ids, out_len, B, T, V, ldv, blank):
                                      V, ldv, blank, _stream()), "ca_ctc_greedy_decode")
 
 
+def ctc_beam_workspace_bytes(B, T, V, beam_width):
+    return lib().ca_ctc_beam_workspace_bytes(B, T, V, beam_width)
+
+
+def ctc_beam_decode(logits, in_len, ids_out, out_len, score_out, ws, B, T, V, ldv, blank, delimiter, forbidden=None,
+                    tables=None, beam_width=100, alpha=0.5, beta=1.5, unk_score_offset=-10.0, token_min_logp=-5.0,
+                    beam_prune_logp=-10.0, score_boundary=True):
+    """CTC prefix beam search with optional n-gram LM fusion (ca_ctc_beam_decode).  `tables`: the dict of
+    `NGramLM.device_tables` on the logits' device, or None for no LM.  `forbidden`: uint8 [V] device mask or None."""
+    d = _lib.CaCtcBeamDesc()
+    d.logits, d.ldv, d.in_len = _p(logits), ldv, _p(in_len)
+    d.B, d.T, d.V, d.blank, d.delimiter = B, T, V, blank, delimiter
+    d.forbidden = _p(forbidden)
+    if tables is not None:
+        d.pfx_keys, d.pfx_wid, d.n_pfx = _p(tables["pfx_keys"]), _p(tables["pfx_wid"]), tables["pfx_keys"].numel()
+        d.ng_keys, d.ng_logp, d.ng_backoff = _p(tables["ng_keys"]), _p(tables["ng_logp"]), _p(tables["ng_backoff"])
+        for k, n in enumerate(tables["ng_count"]):
+            d.ng_count[k] = n
+        d.order, d.bos_wid, d.eos_wid, d.unk_wid = tables["order"], tables["bos_wid"], tables["eos_wid"], tables["unk_wid"]
+    else:
+        d.order, d.bos_wid, d.eos_wid, d.unk_wid = 0, -1, -1, -1
+    d.beam_width = beam_width
+    d.alpha, d.beta, d.unk_score_offset = alpha, beta, unk_score_offset
+    d.token_min_logp, d.beam_prune_logp, d.score_boundary = token_min_logp, beam_prune_logp, int(bool(score_boundary))
+    d.ids_out, d.out_len, d.score_out = _p(ids_out), _p(out_len), _p(score_out)
+    d.ws, d.ws_bytes = _p(ws), ws.numel() * _ELT[ws.dtype]
+    check(lib().ca_ctc_beam_decode(C.byref(d), _stream()), "ca_ctc_beam_decode")
+
+
 def mask_frames(h, tmask, fmask, embed, flen, B, T, Cn):
     check(lib().ca_mask_frames(_p(h), _p(tmask), _p(fmask), _p(embed), _p(flen), B, T, Cn,
                                _stream()), "ca_mask_frames")

@@ -137,3 +137,42 @@ class Wav2Vec2Processor:
             {"do_normalize": True, "feature_size": 1, "padding_value": 0.0, "return_attention_mask": True,
              "sampling_rate": self.feature_extractor.sampling_rate,
              "feature_extractor_type": "Wav2Vec2FeatureExtractor"}, indent=2))
+
+
+class Wav2Vec2ProcessorWithLM(Wav2Vec2Processor):
+    """feature_extractor + tokenizer + n-gram LM (`Wav2Vec2ProcessorWithLM` look-alike, R/src/coral/wav2vec2.py:269-279).
+    Stored as `language_model/{N}gram.arpa` + `language_model/attrs.json` beside the tokenizer files.  `transcribe`
+    decodes with the LM-fused beam search when the processor is of this type; `decoder_params` are the keyword
+    arguments of `Wav2Vec2CTCEngine.beam_decode` (attrs.json over the defaults of coral_amd/ngram.py)."""
+
+    def __init__(self, feature_extractor, tokenizer, lm, decoder_params: dict | None = None):
+        from .ngram import ATTR_KEYS, DEFAULT_PARAMS
+
+        super().__init__(feature_extractor, tokenizer)
+        self.lm = lm
+        self.decoder_params = {k: DEFAULT_PARAMS[k] for k in ATTR_KEYS}
+        self.decoder_params.update(decoder_params or {})
+        self._tables = {}
+
+    def device_tables(self, device) -> dict:
+        key = str(device)
+        if key not in self._tables:
+            self._tables[key] = self.lm.device_tables(self.tokenizer, device)
+        return self._tables[key]
+
+    def save_pretrained(self, model_dir):
+        super().save_pretrained(model_dir)
+        lm_dir = Path(model_dir) / "language_model"
+        lm_dir.mkdir(parents=True, exist_ok=True)
+        self.lm.write_arpa(lm_dir / f"{self.lm.order}gram.arpa")
+        (lm_dir / "attrs.json").write_text(json.dumps(self.decoder_params, indent=2))
+
+    @classmethod
+    def from_pretrained(cls, model_dir, sampling_rate: int = 16_000):
+        from .ngram import NGramLM, find_language_model, load_attrs
+
+        arpa, _ = find_language_model(model_dir)
+        if arpa is None:
+            raise FileNotFoundError(f"{model_dir}/language_model holds no .arpa file")
+        return cls(WaveformFeatureExtractor(sampling_rate), CTCTokenizer.from_pretrained(model_dir),
+                   NGramLM.from_arpa(arpa), load_attrs(arpa.parent))

@@ -815,3 +815,45 @@ class Wav2Vec2CTCEngine:
         ops.ctc_greedy_decode(w["logits"], in_len, raw, ids, olen, B, T, V, Vp, self.s.pad_token_id)
         ids_c, olen_c = ids.cpu(), olen.cpu()
         return [ids_c[b, :int(olen_c[b])].tolist() for b in range(B)], raw
+
+    def beam_decode(self, lm=None, beam_width: int = 100, in_len=None, tokenizer=None, **params):
+        """CTC prefix beam search on the logits of the last forward, fused with the n-gram LM `lm` (the device-table
+        dict of `NGramLM.device_tables`, or an `NGramLM` together with `tokenizer`; None: no LM, for which
+        alpha = beta = 0 is the plain CTC prefix beam search).  `params`: alpha, beta, unk_score_offset,
+        token_min_logp, beam_prune_logp, score_boundary (defaults: coral_amd/ngram.py).  `tokenizer` names the word
+        delimiter and the ids that are never emitted (<s>, </s>, <unk>); without it there are no word boundaries and
+        nothing is forbidden.  -> (ids list per row, scores fp32 [B] = S(y))."""
+        from .ngram import DEFAULT_PARAMS
+
+        sv = self._saved
+        w = sv["w"]
+        B, T, V, Vp = sv["B"], w["T"], self.s.vocab_size, w["Vp"]
+        dev = self.device
+        blank = self.s.pad_token_id
+        if tokenizer is not None:
+            delim = tokenizer.vocab[tokenizer.word_delimiter_token]
+            never = [tokenizer.bos_token_id, tokenizer.eos_token_id, tokenizer.unk_token_id]
+        else:
+            delim, never = -1, []
+        if lm is not None and not isinstance(lm, dict):
+            if tokenizer is None:
+                raise ValueError("beam_decode: an NGramLM needs the tokenizer that spells its words")
+            lm = lm.device_tables(tokenizer, dev)
+        if lm is not None and delim < 0:
+            raise ValueError("beam_decode: LM fusion needs the tokenizer (word delimiter id)")
+        unknown = set(params) - set(DEFAULT_PARAMS)
+        if unknown:
+            raise TypeError(f"beam_decode: unknown parameters {sorted(unknown)}")
+        p = dict(DEFAULT_PARAMS, **params)
+        forbidden = torch.zeros(V, dtype=torch.uint8)
+        for i in never:
+            if 0 <= i < V and i != blank:
+                forbidden[i] = 1
+        ids = torch.empty(B, T, dtype=torch.int32, device=dev)
+        olen = torch.empty(B, dtype=torch.int32, device=dev)
+        score = torch.empty(B, dtype=torch.float32, device=dev)
+        ws = torch.empty(ops.ctc_beam_workspace_bytes(B, T, V, beam_width), dtype=torch.uint8, device=dev)
+        ops.ctc_beam_decode(w["logits"], in_len, ids, olen, score, ws, B, T, V, Vp, blank, delim, forbidden.to(dev), lm,
+                            beam_width=beam_width, **p)
+        ids_c, olen_c = ids.cpu(), olen.cpu()
+        return [ids_c[b, :int(olen_c[b])].tolist() for b in range(B)], score

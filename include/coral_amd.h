@@ -456,6 +456,47 @@ int ca_ctc_greedy_decode(const float* logits, const int32_t* in_len, int32_t* ra
                          int64_t ldv, int32_t blank, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * CTC prefix beam search with n-gram LM fusion (evaluation with `no_lm: false`; the reference decodes through
+ * pyctcdecode, R/src/coral/wav2vec2.py:269-279 - this is the project's own decoder, parity with pyctcdecode is not
+ * pinned).  Objective and search rules: header comment of coral_amd/csrc/ctc_beam.hip and DESIGN.md §8.
+ * One launch per batch, one workgroup per utterance; deterministic (bit-identical ids and score on every run).
+ *   logits fp32 [B,T,ldv] (first V columns valid, 2 <= V <= 256; log_softmax is taken inside); in_len int32 [B] or NULL.
+ *   forbidden uint8 [V] or NULL: ids that are never emitted (<s>, </s>, <unk>).  delimiter = -1: no word boundaries.
+ *   LM tables (coral_amd/ngram.py::NGramLM.device_tables; order = 0 and NULL tables: no LM): pfx_keys uint64 [n_pfx]
+ *   ascending rolling hashes of every prefix of every emittable unigram, pfx_wid int32 [n_pfx] its word id or -1;
+ *   ng_keys uint64 ascending inside each order's segment (segments in order 1..order, ng_count[k] entries for order
+ *   k + 1), ng_logp / ng_backoff fp32 log10 values beside them; bos / eos / unk word ids or -1.
+ *   beam_width 1..128 with beam_width * (V - 1) <= 6144; token_min_logp / beam_prune_logp may be -inf (no pruning).
+ *   ids_out int32 [B,T] (-1 padded), out_len int32 [B], score_out fp32 [B] = S(y) of the returned string.
+ *   ws: ca_ctc_beam_workspace_bytes(B, T, V, beam_width) bytes (back-pointers).  No allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------- */
+typedef struct CaCtcBeamDesc {
+  const float* logits;
+  int64_t ldv;
+  const int32_t* in_len;
+  int32_t B, T, V, blank, delimiter;
+  const uint8_t* forbidden;
+  const uint64_t* pfx_keys;
+  const int32_t* pfx_wid;
+  int64_t n_pfx;
+  const uint64_t* ng_keys;
+  const float* ng_logp;
+  const float* ng_backoff;
+  int64_t ng_count[5];
+  int32_t order, bos_wid, eos_wid, unk_wid;
+  int32_t beam_width;
+  float alpha, beta, unk_score_offset, token_min_logp, beam_prune_logp;
+  int32_t score_boundary;
+  int32_t* ids_out;
+  int32_t* out_len;
+  float* score_out;
+  void* ws;
+  int64_t ws_bytes;
+} CaCtcBeamDesc;
+int64_t ca_ctc_beam_workspace_bytes(int32_t B, int32_t T, int32_t V, int32_t beam_width);
+int ca_ctc_beam_decode(const CaCtcBeamDesc* desc, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Small elementwise pieces of the wav2vec2 encoder.
  * ca_mask_frames: SpecAugment + padding ($TF/.../modeling_wav2vec2.py:1272-1316, 752-755):
  *   h[b,t,:] = embed where tmask[b,t]; h[b,t,c] = 0 where fmask[b,c]; h[b,t,:] = 0 for

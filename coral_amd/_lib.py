@@ -125,7 +125,7 @@ class CaAttnDesc(C.Structure):
                 + [(n, C.c_int32) for n in ("B", "H", "Tq", "Tk", "hd", "Tqp", "causal")]
                 + [("scale", C.c_float), ("dropout_p", C.c_float), ("dropout_seed", C.c_uint64)]
                 + [("O8", C.c_void_p), ("o8_scale", C.c_void_p), ("o8_amax", C.c_void_p),
-                   ("split_ws", C.c_void_p), ("split_ws_bytes", C.c_int64)])
+                   ("split_ws", C.c_void_p), ("split_ws_bytes", C.c_int64), ("row_off", C.c_void_p)])
 
 
 class CaFp8RefreshTask(C.Structure):
@@ -178,6 +178,8 @@ SIGNATURES = {
     "ca_background_update_fits": (C.c_int, [C.POINTER(C.c_int32)]),
     "ca_prof_begin": (C.c_int, []),
     "ca_prof_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "ca_pack_rows": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "ca_unpack_rows": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ca_attn_fwd": (C.c_int, [C.POINTER(CaAttnDesc), _vp]),
     "ca_attn_bwd": (C.c_int, [C.POINTER(CaAttnDesc), _vp]),
     "ca_decode_attn_qproj": (C.c_int, [C.POINTER(CaAttnDesc), _vp, _i64, _vp, _vp, _f32, _vp, _i64, _vp, _i32, _vp]),

@@ -14,6 +14,12 @@ the buffers only a backward reads (LayerNorm statistics, Dq, the FFN pre-activat
 writes only what its next launch consumes and keeps nothing for a backward, and the FFN of M <= 128 rows runs its
 LayerNorm inside fc1's prologue (LN_IN_GEMM).
 
+Packed rows: SelfAttnBlock.forward / .backward and encoder_backward take rows=(row_off, Mp) - the valid
+frames of the B utterances laid end to end, utterance b at rows row_off[b] .. row_off[b + 1] (int32 [B + 1] on the
+device) of every [rows, *] buffer, Mp = row_off[B] as a host integer.  Every GEMM, LayerNorm, column sum and
+weight-gradient problem then runs on Mp rows and the attention kernels address the utterances through
+CaAttnDesc.row_off; T stays the longest utterance's frame count (grid and lse / Dq layout).  None = the [B, T] layout.
+
 fp8: a forward takes its e4m3 operands per call, dict(w=(p8, scale, x8, rs)) for q|k|v / fc1 (the
 e4m3 weights, the matrix's dequantisation factor, the LayerNorm output as e4m3 and its row scales); the training
 forward adds out= / fc2= (the attention / GELU output as e4m3, see WhisperTrainEngine._train_ws) and bwd= / du= (the
@@ -121,18 +127,23 @@ class SelfAttnBlock:
                     ctx=z(B * T * d), lse=z(B * H * Tqp, torch.float32),
                     Dq=z(B * H * Tqp, torch.float32) if train else None, Tqp=Tqp)
 
-    def _akw(self, B, T, Tqp, klen, adrop):
+    def _akw(self, B, T, Tqp, klen, adrop, rows=None):
         d, H = self.d, self.H
         hd = d // H
+        if rows is not None:  # packed rows: the utterance's own length is its key count (no klen)
+            return dict(self._akw(B, T, Tqp, None, adrop), row_off=rows[0])
         return dict(B=B, H=H, Tq=T, Tk=T, hd=hd, Tqp=Tqp, scale=hd ** -0.5, ldq=3 * d, ldk=3 * d, ldv=3 * d, ldo=d,
                     sqb=T * 3 * d, skb=T * 3 * d, svb=T * 3 * d, sob=T * d, q_off=0, k_off=d, v_off=2 * d, klen=klen,
                     causal=self.causal, dropout_p=adrop[0], dropout_seed=adrop[1])
 
-    def forward(self, hin, hout, sv, B, T, klen=None, hdrop=(0.0, 0), adrop=(0.0, 0), fp8=None):
+    def forward(self, hin, hout, sv, B, T, klen=None, hdrop=(0.0, 0), adrop=(0.0, 0), fp8=None, rows=None):
         """hdrop: (p, seed) of the hidden-state dropout on the block's output; adrop: of the dropout on the attention
-        probabilities ($TF/models/whisper/modeling_whisper.py:234); fp8: this call's e4m3 operands (module docstring)."""
+        probabilities ($TF/models/whisper/modeling_whisper.py:234); fp8: this call's e4m3 operands (module docstring);
+        rows: packed rows (module docstring; bf16 path only, klen is then implied)."""
         st, d = self.st, self.d
-        M = B * T
+        M = B * T if rows is None else rows[1]
+        if rows is not None and fp8 is not None:
+            raise ops.CoralAmdError("SelfAttnBlock: packed rows are not implemented on the fp8 path")
         train = sv["st"] is not None
         if fp8 is not None:
             p8, scale, x8, rs = fp8["w"]
@@ -144,7 +155,7 @@ class SelfAttnBlock:
             ops.layernorm_fwd(hin, st.view(self.ln + ".weight"), st.view(self.ln + ".bias"), sv["x"], sv["st"], M, d, self.eps)
             ops.gemm(sv["x"], st.p16, sv["qkv"], M=M, N=3 * d, K=d, lda=d, ldb=d, ldc=3 * d,
                      b_off=st.off(self.attn + "q_proj.weight"), bias=st.p32, bias_off=st.off(self.qbias))
-        akw = self._akw(B, T, sv["Tqp"], klen, adrop)
+        akw = self._akw(B, T, sv["Tqp"], klen, adrop, rows)
         o8 = fp8.get("out") if (fp8 is not None and T >= 100 and adrop[0] == 0.0) else None
         if o8 is not None:
             # out_proj on the fp8 path: the attention kernel's output stage also writes the context as e4m3 (delayed
@@ -159,10 +170,10 @@ class SelfAttnBlock:
                      bias=st.p32, bias_off=st.off(self.attn + "out_proj.bias"), epilogue=EPI_RESIDUAL, R=hin, ldr=d,
                      dropout_p=hdrop[0], dropout_seed=hdrop[1])
         if train:
-            sv.update(hin=hin, klen=klen, hdrop=hdrop, adrop=adrop, fp8=fp8)
+            sv.update(hin=hin, klen=klen, hdrop=hdrop, adrop=adrop, fp8=fp8, rows=rows)
 
     def backward(self, dh, dhin, sv, sc: Scratch, B, T, defer=None, acc=True, sq=None, ln_part=None, pending=None,
-                 dy=None, xdrop=None, deferred=None):
+                 dy=None, xdrop=None, deferred=None, rows=None):
         """dh: grad wrt h_out (kept intact); dhin: output buffer for grad wrt h_in (may alias nothing of sv).
         ln_part / pending: leave the norm's d gamma | d beta partials in `ln_part` and append their second-stage
         reduction to `pending` (the caller runs a layer's reductions as one launch, ops.reduce_rows_multi).
@@ -171,10 +182,11 @@ class SelfAttnBlock:
         they are in the list, before the q|k|v data gradient.  acc=False: the weight gradients overwrite (first
         micro-batch of a step, matrices not cleared); sq: {"o": (slots, off), "qkv": ...} where the weight-gradient GEMMs
         leave their per-tile sums of squares (CaGemmDesc.c_sumsq).  dy: the gradient wrt the output before hidden
-        dropout, computed by the caller (default: dropout(dh) here); xdrop: see layernorm_bwd."""
+        dropout, computed by the caller (default: dropout(dh) here); xdrop: see layernorm_bwd.  rows: the forward's
+        packed rows (module docstring)."""
         sq = sq or {}
         st, d = self.st, self.d
-        M = B * T
+        M = B * T if rows is None else rows[1]
         o, g32, p16 = st.off, st.g32, st.p16
         fb = sv["fp8"].get("bwd") if sv["fp8"] is not None else None
         if dy is None:
@@ -192,7 +204,7 @@ class SelfAttnBlock:
         qkv, dqkv = sv["qkv"], sc.dqkv
         ops.attn_bwd(qkv, qkv, qkv, sv["ctx"], sv["lse"], sc.dctx, sv["Dq"], dqkv, dqkv, dqkv, lddo=d, sdob=T * d, lddq=3 * d,
                      lddk=3 * d, lddv=3 * d, sdqb=T * 3 * d, sdkb=T * 3 * d, sdvb=T * 3 * d, dq_off=0, dk_off=d, dv_off=2 * d,
-                     **self._akw(B, T, sv["Tqp"], sv["klen"], sv["adrop"]))
+                     **self._akw(B, T, sv["Tqp"], sv["klen"], sv["adrop"], rows))
         if defer is None:
             ops.colsum(dqkv, 3 * d, M, 3 * d, g32, sc.part, out_off=o(self.qbias))
         wg.append(dict(dY=dqkv, X=sv["x"], M=3 * d, N=d, K=M, lda=3 * d, ldb=d, c_off=o(self.attn + "q_proj.weight"),
@@ -413,7 +425,7 @@ def norm_plan(store, matrices, device):
 
 
 def encoder_backward(blocks, svs, keep, B, T, ring, scs, bias_ws, ln_parts, *, gm, acc, plan, names, side, wgrad_early,
-                     matrix_range, done, below=None, mring=None, epilogue=None):
+                     matrix_range, done, below=None, mring=None, epilogue=None, rows=None):
     """Backward through a stack of pre-LN encoder layers, blocks[l] = (SelfAttnBlock, FFNBlock) with saved states
     svs[l], from the gradient wrt the stack's output in ring[0] down to the one wrt its input.
 
@@ -429,8 +441,11 @@ def encoder_backward(blocks, svs, keep, B, T, ring, scs, bias_ws, ln_parts, *, g
     below(l) -> (p, seed): the hidden dropout on the output of the sub-layer below layer l (dropped layers skipped).
     With it the LayerNorm backwards also write the dropped gradients of the sub-layers below into `mring` (parallel to
     `ring`; the caller writes mring[0]) and the blocks read them from there; without it each block masks its own.
+    rows: the forward's packed rows (module docstring) - every layer then works on rows[1] rows.
     Returns (the gradient wrt the stack's input, its masked copy or None, a free ring buffer)."""
     main = torch.cuda.current_stream()
+    M = B * T if rows is None else rows[1]
+    kw_rows = {} if rows is None else dict(rows=rows)  # (nothing new in the calls of an unpacked stack)
 
     def on_side(fn):
         """Run fn on the side stream once the main stream has passed this point (in line without a side stream)."""
@@ -472,9 +487,9 @@ def encoder_backward(blocks, svs, keep, B, T, ring, scs, bias_ws, ln_parts, *, g
         def wgrads():
             fused[0] = ops.wgrad_gemm_group(wg, gm, colsum_ws=bw, colsum_ld=nb, Gb=g32)
 
-        ff.backward(ring[i0], ring[i1], sv_f, sc, B * T, defer=wg, acc=acc, sq=sq, ln_part=lnp[0], pending=second, **kw_f)
+        ff.backward(ring[i0], ring[i1], sv_f, sc, M, defer=wg, acc=acc, sq=sq, ln_part=lnp[0], pending=second, **kw_f)
         sa.backward(ring[i1], ring[i2], sv_a, sc, B, T, defer=wg, acc=acc, sq=sq, ln_part=lnp[1], pending=second,
-                    deferred=(lambda: on_side(wgrads)) if wgrad_early else None, **kw_a)
+                    deferred=(lambda: on_side(wgrads)) if wgrad_early else None, **kw_a, **kw_rows)
 
         def finish():
             if not wgrad_early:

@@ -392,6 +392,14 @@ class CoralTrainer:
         return None
 
     # ---- the loop -------------------------------------------------------------------------------------------------
+    def _valid_row_share(self) -> float | None:
+        """Share of the padded frames [B, T] that the wav2vec2 encoder layers processed in the step's last micro-batch
+        (Wav2Vec2CTCEngine.last_rows: below 1 when `pack_frames` dropped the padding); None for other engines."""
+        eng = self.dp.engine
+        if not getattr(eng, "last_rows", 0):
+            return None
+        return eng.last_rows / float(eng.last_frames)
+
     def train(self, resume_from_checkpoint=None, ignore_data_skip: bool | None = None) -> TrainOutput:
         a = self.args
         model_dir = Path(a.output_dir)
@@ -438,7 +446,8 @@ class CoralTrainer:
                                  learning_rate=float(getattr(self.dp, "last_lr", self.dp.lr)), lr=self.dp.lr,
                                  epoch=self.state["epoch"], elapsed=time.time() - t0))
                 if self.is_main:
-                    logger.info("step %d loss %.4f", step + 1, lv)
+                    rows = self._valid_row_share()
+                    logger.info("step %d loss %.4f%s", step + 1, lv, "" if rows is None else " encoder rows %.3f" % rows)
             stop = False
             evaluated = self.eval_dataset is not None and ((step + 1) % a.eval_steps == 0 or step + 1 == a.max_steps)
             if evaluated:

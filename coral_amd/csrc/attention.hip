@@ -303,7 +303,9 @@ struct AttnArgs {
   unsigned int* o8_amax;
   float* lse;                            // [B, H, Tqp]
   const int32_t* klen;                   // [B] or null
+  const int32_t* row_off;                // [B + 1] or null: packed rows (CaAttnDesc.row_off, attn_packed_rows)
   int B, H, Tq, Tk, hd, Tqp, causal;
+  int Tqd, Tkd;                          // strides of the dropout hash: the launch's Tq / Tk (attn_drop_index)
   float scale;
   // backward
   const unsigned short* dO;
@@ -333,8 +335,24 @@ struct AttnArgs {
 // Flat index of probability (b, h, q, key): rows are padded to a multiple of 4 keys so that 4 consecutive keys from a
 // multiple of 4 share one hash (ca_dropout_keep4); the backward kernels regenerate the forward's decisions from it.
 __device__ __forceinline__ uint64_t attn_drop_index(const AttnArgs& a, int b, int h, int q, int key) {
-  const uint64_t tkp = (uint64_t)((a.Tk + 3) & ~3);
-  return (((uint64_t)b * a.H + h) * (uint64_t)a.Tq + (uint64_t)q) * tkp + (uint64_t)key;
+  const uint64_t tkp = (uint64_t)((a.Tkd + 3) & ~3);
+  return (((uint64_t)b * a.H + h) * (uint64_t)a.Tqd + (uint64_t)q) * tkp + (uint64_t)key;
+}
+// Packed rows (CaAttnDesc.row_off): the utterances of a batch lie end to end, utterance b at rows row_off[b] ..
+// row_off[b + 1] of every tensor.  A workgroup turns its copy of the arguments into those of ITS utterance - base
+// pointers moved to its first row, Tq = Tk = its length - so every bound, clamp, tile count, fast-tile count and store
+// predicate below is the utterance's: no load and no store touches a neighbour's rows (the general tile loaders clamp
+// to the utterance's last row, the fast ones only take tiles that are not its last).  lse / Dq stay [B, H, Tqp] indexed
+// by the local query, and the dropout hash keeps the launch's Tq / Tk as strides (Tqd / Tkd): an utterance draws the
+// probability mask of the padded run.  All of it is workgroup-uniform (scalar registers).
+__device__ __forceinline__ void attn_packed_rows(AttnArgs& a, int b) {
+  if (!a.row_off) return;
+  const int64_t r0 = a.row_off[b];
+  const int len = a.row_off[b + 1] - (int)r0;
+  a.Q += r0 * a.ldq; a.K += r0 * a.ldk; a.V += r0 * a.ldv; a.O += r0 * a.ldo;
+  a.dO += r0 * a.lddo; a.dQ += r0 * a.lddq; a.dK += r0 * a.lddk; a.dV += r0 * a.lddv;
+  a.sqb = a.skb = a.svb = a.sob = a.sdob = a.sdqb = a.sdkb = a.sdvb = 0;
+  a.Tq = a.Tk = len;
 }
 
 #define NEG_INF (-__builtin_inff())
@@ -368,7 +386,7 @@ static inline unsigned attn_grid(int ntile, int H, int B) { return (unsigned)(((
 // 1024 workgroups at the path's shape (8 query tiles x 128 heads): at 4 waves per SIMD they are all resident at
 // once; at 3 (148 VGPRs) a second round runs one third full.
 template <int HDPV, bool DROP = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_fwd_kernel(const AttnArgs a) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_fwd_kernel(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NKS = HDPV / 32, NNB = HDPV / 16;
   char* Kimg = smem;                  // K-major image of the key tile
@@ -378,6 +396,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   const int g = lane >> 4, r = lane & 15;
   int tile, h, b;
   if (!attn_tile_of_block((a.Tq + 63) / 64, a.H, a.B, tile, h, b)) return;
+  attn_packed_rows(a, b);
+  if (tile * (64) >= a.Tq) return;  // (packed rows: the tile lies past the utterance)
   const int hd = a.hd;
   const unsigned short* Q = a.Q + b * a.sqb + h * hd;
   const unsigned short* K = a.K + b * a.skb + h * hd;
@@ -532,7 +552,7 @@ __device__ __forceinline__ void wait_vm() {
 // co-resident waves already overlap the two pipes, what is short is issue slots), and four waves per SIMD at 128
 // registers (27 spilled dwords: 183 us).
 template <int HDPV, bool DROP, int NW, int NST, int WPE = 2>
-__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void attn_fwd_wide_kernel(const AttnArgs a) {
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void attn_fwd_wide_kernel(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NQ = 2, NKS = HDPV / 32, NNB = HDPV / 16;
   constexpr int IMG = 64 * HDPV * 2, PAIR = 2 * IMG;  // a tile = K-major image of the keys + MN-major image of the values
@@ -543,6 +563,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
   const int g = lane >> 4, r = lane & 15;
   int tile, h, b;
   if (!attn_tile_of_block((a.Tq + QPB - 1) / QPB, a.H, a.B, tile, h, b)) return;
+  attn_packed_rows(a, b);
+  if (tile * (QPB) >= a.Tq) return;  // (packed rows: the tile lies past the utterance)
   const int hd = a.hd;
   const unsigned short* Q = a.Q + b * a.sqb + h * hd;
   const unsigned short* K = a.K + b * a.skb + h * hd;
@@ -1252,7 +1274,8 @@ __global__ __launch_bounds__(256) void attn_fwd_smallq_kernel(const AttnArgs a) 
 __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(const unsigned short* __restrict__ dO, int64_t lddo,
                                                             int64_t sdob, const unsigned short* __restrict__ O,
                                                             int64_t ldo, int64_t sob, float* __restrict__ Dq, int H,
-                                                            int Tq, int Tqp, int hd, int B) {
+                                                            int Tq, int Tqp, int hd, int B,
+                                                            const int32_t* __restrict__ row_off) {
   // one 16-lane group per (b, h, q)
   const int64_t gid = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;
   const int sub = threadIdx.x & 15;
@@ -1261,6 +1284,12 @@ __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(const unsigned short
   const int q = (int)(gid % Tq);
   const int h = (int)((gid / Tq) % H);
   const int b = (int)(gid / ((int64_t)Tq * H));
+  if (row_off) {  // packed rows (attn_packed_rows): utterance b starts at row row_off[b]; Dq stays indexed by (b, h, q)
+    const int64_t r0 = row_off[b];
+    if (q >= row_off[b + 1] - (int)r0) return;
+    dO += r0 * lddo - b * sdob;
+    O += r0 * ldo - b * sob;
+  }
   const unsigned short* x = dO + b * sdob + (int64_t)q * lddo + h * hd;
   const unsigned short* y = O + b * sob + (int64_t)q * ldo + h * hd;
   float s = 0.f;
@@ -1276,7 +1305,7 @@ __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(const unsigned short
 
 // ---- backward: dK, dV (workgroup = 64 keys, loops over the queries) ------------------------------------
 template <int HDPV, bool DROP = false>
-__global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnArgs a) {
+__global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NKS = HDPV / 32, NNB = HDPV / 16;
   constexpr int IMG = 32 * HDPV * 2;
@@ -1287,6 +1316,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnArgs a) {
   const int g = lane >> 4, r = lane & 15;
   int tile, h, b;
   if (!attn_tile_of_block((a.Tk + 63) / 64, a.H, a.B, tile, h, b)) return;
+  attn_packed_rows(a, b);
+  if (tile * (64) >= a.Tk) return;  // (packed rows: the tile lies past the utterance)
   const int hd = a.hd;
   const unsigned short* Q = a.Q + b * a.sqb + h * hd;
   const unsigned short* K = a.K + b * a.skb + h * hd;
@@ -1458,7 +1489,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnArgs a) {
 // Here a wave owns KB = 2 key blocks: each fragment feeds two MFMAs, a workgroup covers 128 keys, half as many
 // workgroups stream the same Q / dO images.
 template <int HDPV, bool DROP, int KB, int WPE = 2>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void attn_bwd_dkv_wide_kernel(const AttnArgs a) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void attn_bwd_dkv_wide_kernel(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NKS = HDPV / 32, NNB = HDPV / 16;
   constexpr int IMG = 32 * HDPV * 2;
@@ -1469,6 +1500,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
   const int g = lane >> 4, r = lane & 15;
   int tile, h, b;
   if (!attn_tile_of_block((a.Tk + 64 * KB - 1) / (64 * KB), a.H, a.B, tile, h, b)) return;
+  attn_packed_rows(a, b);
+  if (tile * (64 * KB) >= a.Tk) return;  // (packed rows: the tile lies past the utterance)
   const int hd = a.hd;
   const unsigned short* Q = a.Q + b * a.sqb + h * hd;
   const unsigned short* K = a.K + b * a.skb + h * hd;
@@ -1652,7 +1685,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 
 // ---- backward: dQ (workgroup = 64 queries, loops over the keys) ------------------------------------------
 template <int HDPV, bool DROP = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_bwd_dq_kernel(const AttnArgs a) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_bwd_dq_kernel(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NKS = HDPV / 32, NNB = HDPV / 16;
   constexpr int IMG = 64 * HDPV * 2;
@@ -1663,6 +1696,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   const int g = lane >> 4, r = lane & 15;
   int tile, h, b;
   if (!attn_tile_of_block((a.Tq + 63) / 64, a.H, a.B, tile, h, b)) return;
+  attn_packed_rows(a, b);
+  if (tile * (64) >= a.Tq) return;  // (packed rows: the tile lies past the utterance)
   const int hd = a.hd;
   const unsigned short* Q = a.Q + b * a.sqb + h * hd;
   const unsigned short* K = a.K + b * a.skb + h * hd;
@@ -1753,7 +1788,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 // NW waves x 32 queries; per 64-key tile a K-major image of K (S^T = K Q^T and, read transposed, dQ += dS K) and one of
 // V (dP^T = V dO^T): every fragment read feeds the MFMAs of both 16-query blocks of the wave.
 template <int HDPV, bool DROP, int NW, int NST, int WPE = 2>
-__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void attn_bwd_dq_wide_kernel(const AttnArgs a) {
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void attn_bwd_dq_wide_kernel(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NQ = 2, NKS = HDPV / 32, NNB = HDPV / 16;
   constexpr int IMG = 64 * HDPV * 2, PAIR = 2 * IMG;
@@ -1764,6 +1799,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
   const int g = lane >> 4, r = lane & 15;
   int tile, h, b;
   if (!attn_tile_of_block((a.Tq + QPB - 1) / QPB, a.H, a.B, tile, h, b)) return;
+  attn_packed_rows(a, b);
+  if (tile * (QPB) >= a.Tq) return;  // (packed rows: the tile lies past the utterance)
   const int hd = a.hd;
   const unsigned short* Q = a.Q + b * a.sqb + h * hd;
   const unsigned short* K = a.K + b * a.skb + h * hd;
@@ -1936,6 +1973,10 @@ static int attn_check(const CaAttnDesc* d, const char* who) {
   CA_CHECK_ARG((d->ldq % 8) == 0 && (d->ldk % 8) == 0 && (d->ldv % 8) == 0, "%s: strides must be multiples of 8", who);
   CA_CHECK_ARG(d->lse != nullptr && d->Tqp >= d->Tq && (d->Tqp % 32) == 0, "%s: lse needs Tqp %% 32 == 0 rows", who);
   CA_CHECK_ARG(d->dropout_p >= 0.f && d->dropout_p < 1.f, "%s: bad dropout_p", who);
+  // packed rows: self-attention over utterances laid end to end, each with its own length as query and key count
+  CA_CHECK_ARG(d->row_off == nullptr || (d->Tq == d->Tk && !d->causal && d->klen == nullptr && d->O8 == nullptr &&
+                                         d->split_ws == nullptr),
+               "%s: row_off needs Tq == Tk and no causal mask, klen, O8 or split_ws", who);
   return CA_OK;
 }
 static AttnArgs to_args(const CaAttnDesc& d) {
@@ -1944,6 +1985,7 @@ static AttnArgs to_args(const CaAttnDesc& d) {
   a.ldq = d.ldq; a.ldk = d.ldk; a.ldv = d.ldv; a.sqb = d.sqb; a.skb = d.skb; a.svb = d.svb;
   a.O = (unsigned short*)d.O; a.ldo = d.ldo; a.sob = d.sob;
   a.O8 = (unsigned char*)d.O8; a.o8_scale = d.o8_scale; a.o8_amax = (unsigned int*)d.o8_amax;
+  a.row_off = d.row_off; a.Tqd = d.Tq; a.Tkd = d.Tk;
   a.lse = d.lse; a.klen = d.klen; a.B = d.B; a.H = d.H; a.Tq = d.Tq; a.Tk = d.Tk; a.hd = d.hd; a.Tqp = d.Tqp;
   a.causal = d.causal; a.scale = d.scale;
   a.dO = (const unsigned short*)d.dO; a.lddo = d.lddo; a.sdob = d.sdob; a.Dq = d.Dq;
@@ -2065,7 +2107,7 @@ extern "C" int ca_attn_fwd(const CaAttnDesc* desc, void* stream) {
     CA_CHECK_LAUNCH("ca_attn_fwd");
     return CA_OK;
   }
-  if (desc->Tq <= 16 && desc->hd <= 64 && !desc->causal) {  // greedy decoding: the waves split the keys
+  if (desc->Tq <= 16 && desc->hd <= 64 && !desc->causal && !desc->row_off) {  // greedy decoding: the waves split the keys
     constexpr int SMALLQ_LDS = 4 * 3 * 64 * 64 * 2;  // four waves x ring of three 8-KiB V images
     constexpr int SMALLQ_LDS2 = 4 * 2 * 64 * 64 * 2;  // ... of two: two workgroups per CU (large batches)
     static bool attr = false;
@@ -2097,7 +2139,8 @@ extern "C" int ca_decode_attn_qproj(const CaAttnDesc* desc, const void* x, int64
                                     const float* ln_beta, float ln_eps, const void* Wq, int64_t ldw, const float* bq,
                                     int32_t d_model, void* stream) {
   CA_CHECK_ARG(desc && x && ln_gamma && ln_beta && Wq && bq, "ca_decode_attn_qproj: null pointer");
-  CA_CHECK_ARG(desc->K && desc->V && desc->O && desc->B > 0 && desc->H > 0 && desc->Tk > 0, "ca_decode_attn_qproj: bad descriptor");
+  CA_CHECK_ARG(desc->K && desc->V && desc->O && desc->B > 0 && desc->H > 0 && desc->Tk > 0 && !desc->row_off,
+               "ca_decode_attn_qproj: bad descriptor");
   CA_CHECK_ARG(desc->Tq == 1 && desc->hd <= 64 && (desc->hd % 8) == 0 && !desc->causal && desc->dropout_p == 0.f,
                "ca_decode_attn_qproj: one query per clip, head_dim <= 64, no mask, no dropout");
   CA_CHECK_ARG(d_model >= 64 && d_model <= 2048 && (d_model % 8) == 0 && (ldx % 8) == 0 && (ldw % 8) == 0 &&
@@ -2150,7 +2193,8 @@ extern "C" int ca_attn_bwd(const CaAttnDesc* desc, void* stream) {
     const int64_t groups = (int64_t)desc->B * desc->H * desc->Tq;
     hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3((unsigned)((groups * 16 + 255) / 256)), dim3(256), 0, s,
                        (const unsigned short*)desc->dO, desc->lddo, desc->sdob, (const unsigned short*)desc->O,
-                       desc->ldo, desc->sob, (float*)desc->Dq, desc->H, desc->Tq, desc->Tqp, desc->hd, desc->B);
+                       desc->ldo, desc->sob, (float*)desc->Dq, desc->H, desc->Tq, desc->Tqp, desc->hd, desc->B,
+                       desc->row_off);
   }
   static const int dq_wpe3 = [] { const char* e = getenv("CA_ATTN_DQ_WPE3"); return e ? atoi(e) : 1; }();
   if (dq_wide && dq_wpe3 && desc->hd <= 64 && !drop) {

@@ -312,6 +312,56 @@ extern "C" int ca_cast_bf16_f32(const void* x, float* y, int64_t n, void* stream
   return CA_OK;
 }
 
+// ---- packed rows: the valid frames of a padded batch laid end to end ------------------------------------------------
+// x [B, T, row] <-> y [row_off[B], row]: frame t of utterance b is row row_off[b] + t for t < row_off[b + 1] - row_off[b].
+// One thread per 16-byte chunk of a PADDED row (rows of CPR chunks).  PACK reads the valid rows and writes only rows
+// below row_off[B]; unpack writes every padded row, zeros at and past an utterance's length.
+template <bool PACK>
+__global__ __launch_bounds__(256) void pack_rows_kernel(const uint4* __restrict__ x, uint4* __restrict__ y,
+                                                        const int32_t* __restrict__ row_off, int64_t total, int T, int CPR) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int64_t row = i / CPR;
+  const int ch = (int)(i - row * CPR);
+  const int b = (int)(row / T), t = (int)(row - (int64_t)b * T);
+  const int r0 = row_off[b];
+  int len = row_off[b + 1] - r0;
+  len = len < T ? len : T;
+  const int64_t j = (int64_t)(r0 + t) * CPR + ch;
+  if (PACK) {
+    if (t < len) y[j] = x[i];
+  } else {
+    y[i] = t < len ? x[j] : make_uint4(0u, 0u, 0u, 0u);
+  }
+}
+static int pack_rows_launch(bool pack, const void* x, void* y, const int32_t* row_off, int32_t B, int32_t T, int32_t C,
+                            int32_t elt_bytes, void* stream, const char* who) {
+  CA_CHECK_ARG(x && y && row_off && x != y && B > 0 && T > 0 && C > 0, "%s: bad argument", who);
+  CA_CHECK_ARG(elt_bytes == 2 || elt_bytes == 4, "%s: rows of bf16 (2) or fp32 (4) elements", who);
+  const int64_t row_bytes = (int64_t)C * elt_bytes;
+  CA_CHECK_ARG((row_bytes % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0,
+               "%s: rows must be multiples of 16 bytes, 16-byte aligned", who);
+  const int cpr = (int)(row_bytes / 16);
+  const int64_t total = (int64_t)B * T * cpr;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (pack)
+    hipLaunchKernelGGL(pack_rows_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const uint4*)x, (uint4*)y, row_off,
+                       total, T, cpr);
+  else
+    hipLaunchKernelGGL(pack_rows_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, (const uint4*)x, (uint4*)y, row_off,
+                       total, T, cpr);
+  CA_CHECK_LAUNCH(who);
+  return CA_OK;
+}
+extern "C" int ca_pack_rows(const void* x, void* y, const int32_t* row_off, int32_t B, int32_t T, int32_t C,
+                            int32_t elt_bytes, void* stream) {
+  return pack_rows_launch(true, x, y, row_off, B, T, C, elt_bytes, stream, "ca_pack_rows");
+}
+extern "C" int ca_unpack_rows(const void* x, void* y, const int32_t* row_off, int32_t B, int32_t T, int32_t C,
+                              int32_t elt_bytes, void* stream) {
+  return pack_rows_launch(false, x, y, row_off, B, T, C, elt_bytes, stream, "ca_unpack_rows");
+}
+
 // x fp32 [rows][cols] -> y bf16 [cols][rows]; 32x32 LDS tiles
 __global__ __launch_bounds__(256) void transpose_f32_bf16_kernel(const float* __restrict__ x,
                                                                  unsigned short* __restrict__ y,

@@ -176,7 +176,8 @@ class Wav2Vec2ModelSetup(ModelSetup):
             mask_feature_prob=m.mask_feature_prob, mask_feature_length=m.mask_feature_length,
             layerdrop=m.layerdrop, ctc_loss_reduction=m.ctc_loss_reduction, pad_token_id=tok.pad_token_id,
             vocab_size=len(tok.get_vocab()), ctc_zero_infinity=True,
-            freeze_base=bool(m.freeze_feature_encoder), seed=self.config.seed)
+            freeze_base=bool(m.freeze_feature_encoder), seed=self.config.seed,
+            pack_frames=bool(self.config.get("pack_frames", False)))
         return model
 
     def load_data_collator(self) -> DataCollatorCTCWithPadding:

@@ -95,9 +95,12 @@ def hf_config(s: Wav2Vec2Shape, spec: dict) -> dict:
 class Wav2Vec2ForCTC:
     """`Wav2Vec2ForCTC` look-alike backed by `Wav2Vec2CTCEngine` (HIP kernels only)."""
 
-    def __init__(self, shape: Wav2Vec2Shape, device=None, freeze_base=False, spec=None):
+    def __init__(self, shape: Wav2Vec2Shape, device=None, freeze_base=False, spec=None, pack_frames=False):
+        """pack_frames: training steps run the encoder on the valid frames only (Wav2Vec2CTCEngine.pack_frames; the
+        engine's own default, CA_PACK_FRAMES, switches it on as well)."""
         device = device or f"cuda:{torch.cuda.current_device() if torch.cuda.is_available() else 0}"
         self.engine = Wav2Vec2CTCEngine(shape, device, freeze_base=freeze_base)
+        self.engine.pack_frames = bool(pack_frames) or self.engine.pack_frames
         self.shape = shape
         self.spec = spec or dict(apply_spec_augment=False, mask_time_prob=0.0, mask_time_length=10,
                                  mask_feature_prob=0.0, mask_feature_length=64)
@@ -109,6 +112,7 @@ class Wav2Vec2ForCTC:
     def from_pretrained(cls, name_or_path: str, device=None, freeze_base: bool = False, seed: int = 4242,
                         **overrides):
         path = Path(name_or_path)
+        pack = bool(overrides.pop("pack_frames", False))
         spec = {k: overrides.pop(k) for k in ("apply_spec_augment", "mask_time_prob", "mask_time_length",
                                               "mask_feature_prob", "mask_feature_length") if k in overrides}
         if path.is_dir() and (path / "config.json").exists():
@@ -126,7 +130,7 @@ class Wav2Vec2ForCTC:
                 ctc_loss_reduction=overrides.get("ctc_loss_reduction", cfg.get("ctc_loss_reduction", "sum")),
                 ctc_zero_infinity=overrides.get("ctc_zero_infinity", cfg.get("ctc_zero_infinity", True)),
                 layerdrop=overrides.get("layerdrop", cfg.get("layerdrop", 0.0)), **drops)
-            model = cls(shape, device, freeze_base, spec)
+            model = cls(shape, device, freeze_base, spec, pack)
             rep = model.engine.load_state_dict(load_checkpoint_tensors(path), strict=False, seed=seed)
             if rep["missing"]:
                 logger.warning("%s: %s newly initialised (not in the checkpoint, or of another size)", path, rep["missing"])
@@ -144,7 +148,7 @@ class Wav2Vec2ForCTC:
                               layerdrop=overrides.get("layerdrop", 0.0), **drops)
         logger.warning("no network / hub cache here: %s is instantiated with seeded random weights "
                        "(pass a local directory holding model.safetensors for real weights)", name_or_path)
-        model = cls(shape, device, freeze_base, spec)
+        model = cls(shape, device, freeze_base, spec, pack)
         model.init_weights(seed)
         return model
 

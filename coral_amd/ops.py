@@ -588,6 +588,22 @@ def cast_f32_bf16(x, y, n, x_off=0, y_off=0):
     check(lib().ca_cast_f32_bf16(_p(x, x_off), _p(y, y_off), n, _stream()), "ca_cast_f32_bf16")
 
 
+def pack_rows(x, y, row_off, B, T, Cn):
+    """x [B, T, Cn] (bf16 or fp32) -> y [row_off[B], Cn]: the first row_off[b + 1] - row_off[b] frames of every utterance
+    laid end to end (row_off int32 [B + 1] on the device).  Rows of y at or past row_off[B] are not written."""
+    if x.dtype != y.dtype:
+        raise CoralAmdError("pack_rows: x and y must have the same dtype")
+    check(lib().ca_pack_rows(_p(x), _p(y), _p(row_off), B, T, Cn, _ELT[x.dtype], _stream()), "ca_pack_rows")
+
+
+def unpack_rows(x, y, row_off, B, T, Cn):
+    """The inverse of pack_rows: y [B, T, Cn] from the packed rows x, zeros in every frame at or past its utterance's
+    length."""
+    if x.dtype != y.dtype:
+        raise CoralAmdError("unpack_rows: x and y must have the same dtype")
+    check(lib().ca_unpack_rows(_p(x), _p(y), _p(row_off), B, T, Cn, _ELT[x.dtype], _stream()), "ca_unpack_rows")
+
+
 def cast_bf16_f32(x, y, n):
     check(lib().ca_cast_bf16_f32(_p(x), _p(y), n, _stream()), "ca_cast_bf16_f32")
 
@@ -739,8 +755,9 @@ def prof_end():
 
 def _attn_desc(Q, K, V, O, lse, *, B, H, Tq, Tk, hd, Tqp, scale, ldq, ldk, ldv, ldo, sqb, skb, svb, sob,
                q_off=0, k_off=0, v_off=0, o_off=0, klen=None, causal=False, dropout_p=0.0, dropout_seed=0,
-               O8=None, o8_scale=None, o8_amax=None, split_ws=None):
+               O8=None, o8_scale=None, o8_amax=None, split_ws=None, row_off=None):
     d = CaAttnDesc()
+    d.row_off = _p(row_off)  # packed rows: utterance b at rows row_off[b] .. row_off[b + 1] (Tq = Tk = the longest)
     if split_ws is not None:  # key split of the small-query kernel (attn_split_workspace)
         d.split_ws, d.split_ws_bytes = _p(split_ws), split_ws.numel() * _ELT[split_ws.dtype]
     if O8 is not None:  # the output also as e4m3 (delayed per-tensor scale): the fp8 operand of the out-projection

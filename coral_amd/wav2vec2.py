@@ -13,7 +13,10 @@ HBM layout
   * activations: channels-last [B*T, C] bf16; q,k,v of a layer live in one [B*T, 3d] matrix; the encoder
     layers are blocks.SelfAttnBlock + blocks.FFNBlock (fused attention, no [T, T] matrix in HBM);
   * conv layers 1..6 and the grouped positional conv run as implicit GEMMs over overlapping-row
-    views (no im2col is ever materialised in the forward pass).
+    views (no im2col is ever materialised in the forward pass);
+  * packed mode (`pack_frames`): in a training step with labels the valid frames of the batch are laid
+    end to end behind the positional conv, and the encoder layers, the final LayerNorm and lm_head run on those
+    Mp = sum(flen) rows - a prefix of the same [B*T, C] buffers; logits and the gradient wrt h[0] return to [B, T, *].
 """
 
 from __future__ import annotations
@@ -79,6 +82,18 @@ def _r8(n: int) -> int:
 # ($TF/models/wav2vec2/modeling_wav2vec2.py:291-298,429-434): 0.5 GB more at B = 8 and seven bf16 roundings less in front
 # of the transformer.  CA_CONV_F32=0 restores the bf16 tensors (A/B measurements only).
 CONV_F32 = os.environ.get("CA_CONV_F32", "1") == "1"
+
+
+def frame_row_offsets(attention_mask: torch.Tensor, conv_kernel, conv_stride):
+    """Host attention mask [B, N] -> (flen int64 [B], row_off int32 [B + 1]): the frames every utterance has behind the
+    conv stack (`_get_feat_extract_output_lengths` of its sample count) and their cumulative sums, row_off[0] = 0 - where
+    utterance b starts when the valid frames of the batch are laid end to end (row_off[B] = their number)."""
+    n = attention_mask.to(torch.int64).sum(-1)
+    for k, st in zip(conv_kernel, conv_stride):
+        n = torch.div(n - k, st, rounding_mode="floor") + 1
+    row_off = torch.zeros(n.numel() + 1, dtype=torch.int32)
+    row_off[1:] = torch.cumsum(n, 0)
+    return n, row_off
 
 
 def _arena_build(build, device, default_dtype):
@@ -250,6 +265,10 @@ class Wav2Vec2CTCEngine:
                          p + "feed_forward.output_dense", s.hidden_size, s.intermediate_size, s.layer_norm_eps)))
         self.freeze_base = freeze_base
         self.training = False
+        # packed mode (forward()): the encoder of a training step works on the valid frames only
+        self.pack_frames = os.environ.get("CA_PACK_FRAMES", "0") not in ("", "0")
+        self.last_rows = 0  # rows the encoder layers processed in the last forward: sum(flen) when packed, else B * T
+        self.last_frames = 0  # ... and B * T of that forward
         self._ws = None
         self._ws_key = None
         self._stager = PinnedStager(self.device)
@@ -480,6 +499,7 @@ class Wav2Vec2CTCEngine:
             w["xg"] = z(B * G * (T + K) * Cg + 8 * Cg)
             w["pc_pre"] = z(M * d)
             w["h"] = [z(M * d) for _ in range(L + 1)]      # residual stream entering layer l (h[L] = out)
+            w["hpk"] = z(M * d)                            # packed mode: the valid rows of h[0], laid end to end
             w["h1"] = [z(M * d) for _ in range(L)]         # ... between layer l's attention and feed-forward blocks
             w["sv"] = [(sa.alloc(B, T, z), ff.alloc(M, z)) for sa, ff in self.blocks]  # the blocks' saved activations
             w["hf"] = z(M * d)
@@ -489,6 +509,7 @@ class Wav2Vec2CTCEngine:
             w["logits"] = z(M * Vp, dt=f32)
             w["dlogits"] = z(M * Vp, dt=f32)
             w["dlogits16"] = z(M * Vp)
+            w["dlogits16p"] = z(M * Vp)                    # packed mode: the valid rows of dlogits16
             w["nll"] = z(B, dt=f32)
             # backward scratch
             w["dA"] = z(M * d)
@@ -530,7 +551,20 @@ class Wav2Vec2CTCEngine:
     def forward(self, input_values, attention_mask=None, labels=None, mask_time=None,
                 mask_feature=None, layer_keep=None) -> CTCOutput:
         """input_values f32 [B,N] (already zero-mean/unit-var: the reference's feature extractor
-        output), attention_mask [B,N] or None, labels i64/i32 [B,L] (-100 padded) or None."""
+        output), attention_mask [B,N] or None, labels i64/i32 [B,L] (-100 padded) or None.
+
+        Packed mode: with `pack_frames` set, in training mode, with labels and at least one padded frame in the batch,
+        the rows behind the positional conv are the valid frames only (`last_rows` = their number Mp < B * T): the
+        `pos_conv` dropout site still draws on the [B, T, d] layout, then h[0] is packed, the layers, the final LayerNorm,
+        the `final` dropout and lm_head run on Mp rows and the logits are scattered back into [B, T, V] (frames at or past
+        an utterance's length hold 0; unpacked they hold what the padding computes - CTC reads neither).  Loss and
+        gradients are those of the unpacked step up to rounding: a padded frame is never a key, never reaches the loss
+        and so carries no gradient.  The elementwise dropout sites inside the packed region (attn_out, ffn_out, final,
+        activation dropout) hash the packed flat index - another, equally valid draw than the unpacked step's; the
+        attention-probability masks are the unpacked step's.  The row offsets are built on the host from the
+        attention mask (the collator's host tensor: no extra transfer beyond staging B + 1 integers); a mask that
+        already lives on the device costs one B-integer device-to-host copy, which waits for the stream.  Evaluation
+        forwards, forwards without labels and full batches take the unpacked launches, bit for bit."""
         s, st = self.s, self.store
         dev = self.device
         x = self._stager.to_device(input_values, torch.float32, "x")
@@ -553,6 +587,22 @@ class Wav2Vec2CTCEngine:
             flen = w["flen_full"]
         keep = [True] * L if layer_keep is None else list(layer_keep)
         w["flen"] = flen
+        rows = None  # packed mode: (row_off int32 [B + 1] on the device, Mp)
+        if self.pack_frames and self.training and labels is not None and attention_mask is not None:
+            if attention_mask.device.type == "cpu":
+                fl, row_off = frame_row_offsets(attention_mask, s.conv_kernel, s.conv_stride)
+            else:  # (the B-integer device-to-host copy: the frame lengths the kernel above just produced)
+                fl = flen.cpu().to(torch.int64)
+                row_off = torch.zeros(B + 1, dtype=torch.int32)
+                row_off[1:] = torch.cumsum(fl, 0)
+            Mp = int(row_off[B])
+            # (an utterance without a frame, or lengths beyond T, are not this path's business; Mp == M: nothing to drop,
+            # and the attention kernels' tile loads are promised rows behind Mp inside the buffers)
+            if int(fl.min()) >= 1 and int(fl.max()) <= T and Mp < M:
+                rows = (self._stager.to_device(row_off, torch.int32, "row_off"), Mp)
+        Me = M if rows is None else rows[1]  # rows of the encoder layers and the head
+        kw_rows = {} if rows is None else dict(rows=rows)
+        self.last_rows, self.last_frames = Me, M
         self._await("front")
 
         # feature encoder
@@ -600,35 +650,43 @@ class Wav2Vec2CTCEngine:
         pa = self.dropout_site("pos_conv")
         if pa[0] > 0:  # (hidden dropout on the sum h0 + pos_conv(h0): layer 0 and its LN backward read the dropped values)
             ops.dropout(w["h"][0], w["h"][0], M * d, *pa)
+        hs = w["h"]
+        if rows is not None:
+            ops.pack_rows(w["h"][0], w["hpk"], rows[0], B, T, d)
+            hs = [w["hpk"]] + w["h"][1:]
         # encoder layers
         drop_p = s.activation_dropout if self.training else 0.0
         for l, (sa, ff) in enumerate(self.blocks):
-            hin, hout = w["h"][l], w["h"][l + 1]
+            hin, hout = hs[l], hs[l + 1]
             if not keep[l]:
-                hout.copy_(hin)
+                hout[:Me * d].copy_(hin[:Me * d])
                 continue
             self._await(f"layer{l}")
             sv_a, sv_f = w["sv"][l]
             sa.forward(hin, w["h1"][l], sv_a, B, T, klen=flen, hdrop=self.dropout_site("attn_out", l),
-                       adrop=self.dropout_site("attention", l))
-            ff.forward(w["h1"][l], hout, sv_f, M, drop_p, self.step_seed * 1000 + l, hdrop=self.dropout_site("ffn_out", l))
+                       adrop=self.dropout_site("attention", l), **kw_rows)
+            ff.forward(w["h1"][l], hout, sv_f, Me, drop_p, self.step_seed * 1000 + l, hdrop=self.dropout_site("ffn_out", l))
         # final LN + lm_head (fp32 logits, ld = Vp)
         self._await("head")
         for l in range(L):  # dropped layers were not waited for above; the backward reads every layer's weights
             if not keep[l]:
                 self._await(f"layer{l}")
-        ops.layernorm_fwd(w["h"][L], st.view("wav2vec2.encoder.layer_norm.weight"),
-                          st.view("wav2vec2.encoder.layer_norm.bias"), w["hf"], w["stf"], M, d, eps)
+        ops.layernorm_fwd(hs[L], st.view("wav2vec2.encoder.layer_norm.weight"),
+                          st.view("wav2vec2.encoder.layer_norm.bias"), w["hf"], w["stf"], Me, d, eps)
         pz = self.dropout_site("final")
         if pz[0] > 0:  # in place: lm_head and its weight gradient both read the dropped values
-            ops.dropout(w["hf"], w["hf"], M * d, *pz)
+            ops.dropout(w["hf"], w["hf"], Me * d, *pz)
         V = s.vocab_size
-        ops.gemm(w["hf"], p16, w["logits"], M=M, N=V, K=d, lda=d, ldb=d, ldc=Vp,
+        # (packed: the Mp logit rows land in the dlogits buffer - CTC writes it only afterwards - and are scattered from
+        # there into the [B, T, Vp] buffer CTC and the caller read, zeros in the padded frames)
+        ops.gemm(w["hf"], p16, w["logits"] if rows is None else w["dlogits"], M=Me, N=V, K=d, lda=d, ldb=d, ldc=Vp,
                  b_off=o("lm_head.weight"), bias=p32, bias_off=o("lm_head.bias"))
+        if rows is not None:
+            ops.unpack_rows(w["dlogits"], w["logits"], rows[0], B, T, Vp)
         logits = w["logits"].view(B, T, Vp)[:, :, :V]
         out = CTCOutput(logits=logits, loss=None)
         self._saved = dict(w=w, x=x, flen=flen, keep=keep, tm=tm, fm=fm, B=B, N=N,
-                           has_loss=False, training=self.training)
+                           has_loss=False, training=self.training, rows=rows, hs=hs)
         if labels is not None:
             lab = self._stager.to_device(labels, torch.int32, "lab")
             Lmax = lab.shape[1]
@@ -686,33 +744,42 @@ class Wav2Vec2CTCEngine:
             ops.wave_scale(dl, self._scale_scalar(loss_scale), dl, 1, M * Vp)
         ops.cast_f32_bf16(dl, w["dlogits16"], M * Vp)
         d16 = w["dlogits16"]
-        ops.gemm(d16, w["hf"], g32, M=V, N=d, K=M, a_layout=MNMAJOR, lda=Vp, b_layout=MNMAJOR, ldb=d,
+        # packed mode: the head and the encoder layers on the forward's Mp valid rows (Me), the rest on [B, T]
+        rows, hs = sv["rows"], sv["hs"]
+        Me = M if rows is None else rows[1]
+        if rows is not None:
+            ops.pack_rows(d16, w["dlogits16p"], rows[0], B, T, Vp)
+            d16 = w["dlogits16p"]
+        ops.gemm(d16, w["hf"], g32, M=V, N=d, K=Me, a_layout=MNMAJOR, lda=Vp, b_layout=MNMAJOR, ldb=d,
                  ldc=d, c_off=o("lm_head.weight"), out_f32=True, accumulate=acc)
-        ops.colsum(d16, Vp, M, Vp, g32, part, out_off=o("lm_head.bias"))
+        ops.colsum(d16, Vp, Me, Vp, g32, part, out_off=o("lm_head.bias"))
         if self.freeze_base:
             done("head")
             return
-        ops.gemm(d16, p16, w["dA"], M=M, N=d, K=V, lda=Vp, b_layout=MNMAJOR, ldb=d, ldc=d,
+        ops.gemm(d16, p16, w["dA"], M=Me, N=d, K=V, lda=Vp, b_layout=MNMAJOR, ldb=d, ldc=d,
                  b_off=o("lm_head.weight"))
         tr = sv["training"]
         pz = self.dropout_site("final", training=tr)
         if pz[0] > 0:
-            ops.dropout(w["dA"], w["dA"], M * d, *pz)
+            ops.dropout(w["dA"], w["dA"], Me * d, *pz)
 
         def branch_site(j):
             """(p, seed) of the hidden dropout whose output the residual stream h[j] carries: the FFN-output site of the
             highest kept layer below j, or the one on h0 + pos_conv(h0) when there is none (dropped layers are the
             identity and draw no masks)."""
             below = [k for k in range(j) if keep[k]]
+            if not below and rows is not None:
+                # packed: the pos_conv site drew on [B, T, d] - its mask meets the gradient after the unpack below
+                return 0.0, 0
             return self.dropout_site("ffn_out", below[-1], tr) if below else self.dropout_site("pos_conv", training=tr)
 
         ring, mring = w["ring"], w["mring"]
         # ring[0]: the gradient wrt the residual stream leaving layer L-1; mring[0]: dropout(ring[0]) with the mask of the
         # hidden-dropout site whose output that stream carries - the gradient of that site's branch
         drop = branch_site(L)
-        layernorm_bwd(w["dA"], w["h"][L], st.view("wav2vec2.encoder.layer_norm.weight"), w["stf"], None, ring[0],
+        layernorm_bwd(w["dA"], hs[L], st.view("wav2vec2.encoder.layer_norm.weight"), w["stf"], None, ring[0],
                       st.view("wav2vec2.encoder.layer_norm.weight", "g32"), st.view("wav2vec2.encoder.layer_norm.bias", "g32"),
-                      part, M, d, (*drop, mring[0]) if drop[0] > 0 else None)
+                      part, Me, d, (*drop, mring[0]) if drop[0] > 0 else None)
         done("head")
         # Weight gradients on their own stream: dW = dY^T X feeds only the optimiser, so a layer's weight-gradient launch
         # (MFMA-bound, 256x256 tiles, one workgroup per CU) runs beside the NEXT layer's data-gradient chain (128x128-tile
@@ -721,13 +788,22 @@ class Wav2Vec2CTCEngine:
         dh, dhm, dpc = encoder_backward(
             self.blocks, w["sv"], keep, B, T, ring, w["scs"], w["bias_ws"], w["ln_partial"], gm=gm, acc=lacc,
             plan=self.norm_plan(), names=[f"layer{l}" for l in range(L)], side=wgrad_stream(self), wgrad_early=True,
-            matrix_range=lambda l: self.shard_ranges()[f"layer{l}"], done=done, below=branch_site, mring=mring)
+            matrix_range=lambda l: self.shard_ranges()[f"layer{l}"], done=done, below=branch_site, mring=mring,
+            **({} if rows is None else dict(rows=rows)))
         # dh: gradient wrt h[0] = h0m + gelu(pc_pre)
         G, K = s.num_conv_pos_embedding_groups, s.num_conv_pos_embeddings
         Cg = d // G
         Tpad = T + K
         # (hidden dropout on h0 + pos_conv(h0): both terms see the masked gradient)
         dg = dhm if branch_site(0)[0] > 0 else dh
+        if rows is not None:
+            # back to [B, T, d] (zeros in the padded frames) in a ring buffer nothing uses any more, then the pos_conv
+            # site's mask
+            dg = next(r for r in ring if r is not dh and r is not dpc)
+            ops.unpack_rows(dh, dg, rows[0], B, T, d)
+            pc = self.dropout_site("pos_conv", training=tr)
+            if pc[0] > 0:
+                ops.dropout(dg, dg, M * d, *pc)
         ops.dgelu_mul(dg, w["pc_pre"], dpc, M * d)
         ops.colsum(dpc, d, M, d, g32, part, out_off=o("wav2vec2.encoder.pos_conv_embed.conv.bias"))
         # weight gradient in GEMM layout [G][Cg][K][Cg], then through the weight norm

@@ -419,6 +419,15 @@ typedef struct CaAttnDesc {
    * a time per workspace.  NULL = one workgroup per (clip, head). */
   void* split_ws;
   int64_t split_ws_bytes;
+  /* Packed rows (optional; NULL = the [B, T, *] layout above): B + 1 cumulative row counts on the device.  The
+   * utterances lie end to end - utterance b's rows of Q / K / V / O / dO / dQ / dK / dV start at row row_off[b] (times
+   * the tensor's row stride; the batch strides s?b are not used) and its query AND key count is row_off[b + 1] -
+   * row_off[b], at most Tq.  Tq (== Tk) is the longest utterance and sizes the grid; lse / Dq stay [B, H, Tqp] indexed by
+   * the utterance's own query index, and attention dropout hashes (b, h, query, key) with Tq / Tk as strides, so an
+   * utterance draws the mask of the padded launch.  No row outside an utterance's range is written by its workgroups
+   * and no row at or past row_off[B] is read or written.  Self-attention only: not causal, klen, O8 and split_ws
+   * NULL - anything else is CA_ERR_ARG. */
+  const int32_t* row_off;
 } CaAttnDesc;
 #define CA_ATTN_SPLIT_MAX 4
 #define CA_ATTN_SPLIT_WS_BYTES(B, H) \
@@ -519,6 +528,16 @@ int ca_posconv_weight(const float* v, const float* g, void* wf, void* wb, float*
 int ca_posconv_weight_bwd(const float* dwf, const float* v, const float* g,
                           const float* norm, float* dv, float* dg, float* partial, int32_t d,
                           int32_t Cg, int32_t K, void* stream);
+
+/* Packed rows: the valid frames of a padded batch laid end to end (CaAttnDesc.row_off).  row_off int32 [B + 1] on the
+ * device, cumulative frame counts, 0 <= row_off[b + 1] - row_off[b] <= T.  Rows of C elements of elt_bytes (2: bf16,
+ * 4: fp32), C * elt_bytes a multiple of 16, both buffers 16-byte aligned and distinct.
+ * ca_pack_rows:   y[row_off[b] + t, :] = x[b, t, :] for t < len[b]; nothing else of y is written.
+ * ca_unpack_rows: y[b, t, :] = x[row_off[b] + t, :] for t < len[b], 0 for the other frames of [B, T]. */
+int ca_pack_rows(const void* x, void* y, const int32_t* row_off, int32_t B, int32_t T, int32_t C, int32_t elt_bytes,
+                 void* stream);
+int ca_unpack_rows(const void* x, void* y, const int32_t* row_off, int32_t B, int32_t T, int32_t C, int32_t elt_bytes,
+                   void* stream);
 
 /* casts / transposes used when refreshing bf16 compute copies from fp32 masters */
 int ca_cast_f32_bf16(const float* x, void* y, int64_t n, void* stream);

@@ -119,7 +119,7 @@ def decode_ws_bytes(B, d, f, H, n_layers):
 class CaAttnDesc(C.Structure):
     """Mirror of `CaAttnDesc` in include/coral_amd.h."""
 
-    _fields_ = ([(n, C.c_void_p) for n in ("Q", "K", "V", "O", "dO", "dQ", "dK", "dV", "lse", "Dq", "klen")]
+    _fields_ = ([(n, C.c_void_p) for n in ("Q", "K", "V", "O", "dO", "dQ", "dK", "dV", "lse", "Dq", "klen", "key_slot")]
                 + [(n, C.c_int64) for n in ("ldq", "ldk", "ldv", "ldo", "lddo", "lddq", "lddk", "lddv",
                                              "sqb", "skb", "svb", "sob", "sdob", "sdqb", "sdkb", "sdvb")]
                 + [(n, C.c_int32) for n in ("B", "H", "Tq", "Tk", "hd", "Tqp", "causal")]
@@ -151,6 +151,17 @@ class CaCtcBeamDesc(C.Structure):
                 ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
 
+class CaBeamDesc(C.Structure):
+    """Mirror of `CaBeamDesc` in include/coral_amd.h."""
+
+    _fields_ = ([(n, C.c_int32) for n in ("B", "k", "max_len", "prompt_len", "max_length", "eos_id", "early_stopping")]
+                + [(n, C.c_void_p) for n in ("len_pen", "cand_score", "cand_parent", "cand_token", "run_score", "tok", "pos",
+                                              "klen", "anc_in", "anc_out", "ids_in", "ids_out", "fin_score", "fin_len",
+                                              "fin_seq", "fin_ids", "fin_count", "heur", "done", "tr_parent", "tr_token",
+                                              "tr_score")])
+
+
+BEAM_MAX_BEAMS, BEAM_MAX_ROWS = 16, 128  # CA_BEAM_MAX_BEAMS, CA_BEAM_MAX_ROWS
 FP8_GROUP_MAX = 8  # CA_FP8_GROUP_MAX
 KMAJOR, MNMAJOR = 0, 1
 EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_DGELU, EPI_GELU_RESIDUAL = 0, 1, 2, 3, 4
@@ -233,6 +244,9 @@ SIGNATURES = {
     ),
     "ca_ctc_beam_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "ca_ctc_beam_decode": (C.c_int, [C.POINTER(CaCtcBeamDesc), _vp]),
+    "ca_beam_select_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "ca_beam_select": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ca_beam_advance": (C.c_int, [C.POINTER(CaBeamDesc), _vp]),
     "ca_mask_frames": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "ca_regroup_pad": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "ca_posconv_partial_floats": (_i64, [_i32]),

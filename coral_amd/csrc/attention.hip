@@ -303,6 +303,7 @@ struct AttnArgs {
   unsigned int* o8_amax;
   float* lse;                            // [B, H, Tqp]
   const int32_t* klen;                   // [B] or null
+  const int32_t* key_slot;               // [B, Tk] or null: small-query kernel, the cache row of each key (CaAttnDesc.key_slot)
   const int32_t* row_off;                // [B + 1] or null: packed rows (CaAttnDesc.row_off, attn_packed_rows)
   int B, H, Tq, Tk, hd, Tqp, causal;
   int Tqd, Tkd;                          // strides of the dropout hash: the launch's Tq / Tk (attn_drop_index)
@@ -879,7 +880,10 @@ __device__ __forceinline__ void glds16_async(const void* g, char* lds_wave_base)
 // at most about two per CU; 2 (64 KiB: two workgroups per CU) for larger batches (round 5: an evaluation batch of 64
 // clips x 16 heads is 1024 workgroups - with one per CU they ran in four rounds, each paying its LayerNorm + query
 // projection prologue in front of its K|V stream; with two per CU one workgroup's prologue runs under the other's stream).
-template <int HDPV, bool QP = false, int DT = 3>
+// KS (CaAttnDesc.key_slot, beam search): key / value t of query row b comes from cache row key_slot[b, t] instead of row b.
+// The row's table is copied into LDS behind the V rings before the first tile is asked for, so the loop's address
+// arithmetic gains one LDS read per row and its vector-memory sequence - and the counted waits - stay what they are.
+template <int HDPV, bool QP = false, int DT = 3, bool KS = false>
 __global__ __launch_bounds__(256) void attn_fwd_smallq_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NKS = HDPV / 32, NNB = HDPV / 16;
@@ -900,12 +904,22 @@ __global__ __launch_bounds__(256) void attn_fwd_smallq_kernel(const AttnArgs a) 
   const int vw = sp * 4 + wave, nvw = 4 * ns;  // this wave's place among the waves that share the keys
   const int hd = a.hd;
   const unsigned short* Q = QP ? nullptr : a.Q + b * a.sqb + h * hd;
-  const unsigned short* K = a.K + b * a.skb + h * hd;
-  const unsigned short* V = a.V + b * a.svb + h * hd;
+  const unsigned short* K = a.K + (KS ? 0 : b * a.skb) + h * hd;
+  const unsigned short* V = a.V + (KS ? 0 : b * a.svb) + h * hd;
   char* Vring = smem + wave * D * IMG;
   const int qrow = r < a.Tq ? r : a.Tq - 1;
   int kl = a.Tk;
   if (a.klen) kl = a.klen[b] < kl ? a.klen[b] : kl;
+  const int* slot = (const int*)(smem + 4 * D * IMG);  // KS: [Tk] cache rows of this query row's keys
+  if constexpr (KS) {
+    int* sw = (int*)(smem + 4 * D * IMG);
+    for (int t = threadIdx.x; t < a.Tk; t += 256) {
+      int sl = t < kl ? a.key_slot[(int64_t)b * a.Tk + t] : b;  // (keys past klen are loaded clamped and masked: own row)
+      sl = sl < 0 ? 0 : (sl >= a.B ? a.B - 1 : sl);           // no table entry can take a load outside the cache
+      sw[t] = sl;
+    }
+    __syncthreads();
+  }
   bf16x8_t qf[NKS];
   if constexpr (QP) {
     const int C = a.qp_d, nchunk = C >> 3;
@@ -1033,7 +1047,8 @@ __global__ __launch_bounds__(256) void attn_fwd_smallq_kernel(const AttnArgs a) 
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks) {
         const int dim = 32 * ks + 8 * g;
-        kf[S][blk][ks] = gload16_async(K + (int64_t)key * a.ldk + (dim < hd ? dim : 0));
+        kf[S][blk][ks] = gload16_async(K + (KS ? (int64_t)slot[key] * a.skb : (int64_t)0) + (int64_t)key * a.ldk +
+                                       (dim < hd ? dim : 0));
       }
     }
     constexpr int PC = HDPV / 8, RPI = 64 / PC;
@@ -1044,8 +1059,9 @@ __global__ __launch_bounds__(256) void attn_fwd_smallq_kernel(const AttnArgs a) 
       const int c = (lane % PC) ^ mnswz<PC>(kr);
       const int dim = c * 8;
       const int row = kt * 64 + kr;
-      const void* src = (row < a.Tk && dim < hd) ? (const void*)(V + (int64_t)row * a.ldv + dim)
-                                                 : (const void*)g_attn_zero_page;
+      const void* src = (row < a.Tk && dim < hd)
+                            ? (const void*)(V + (KS ? (int64_t)slot[row] * a.svb : (int64_t)0) + (int64_t)row * a.ldv + dim)
+                            : (const void*)g_attn_zero_page;
       glds16_async(src, img + i * 1024);
     }
   };
@@ -1977,6 +1993,12 @@ static int attn_check(const CaAttnDesc* d, const char* who) {
   CA_CHECK_ARG(d->row_off == nullptr || (d->Tq == d->Tk && !d->causal && d->klen == nullptr && d->O8 == nullptr &&
                                          d->split_ws == nullptr),
                "%s: row_off needs Tq == Tk and no causal mask, klen, O8 or split_ws", who);
+  // cache rows by table: the single-query decode form only (attn_fwd_smallq_kernel<.., KS>)
+  CA_CHECK_ARG(d->key_slot == nullptr ||
+                   (d->Tq == 1 && d->klen != nullptr && d->hd <= 64 && !d->causal && d->dropout_p == 0.f &&
+                    d->O8 == nullptr && d->split_ws == nullptr && d->row_off == nullptr && d->Tk <= 4096),
+               "%s: key_slot needs Tq == 1, klen, head_dim <= 64, Tk <= 4096 and no causal mask, dropout, O8, split_ws or "
+               "row_off", who);
   return CA_OK;
 }
 static AttnArgs to_args(const CaAttnDesc& d) {
@@ -1986,7 +2008,7 @@ static AttnArgs to_args(const CaAttnDesc& d) {
   a.O = (unsigned short*)d.O; a.ldo = d.ldo; a.sob = d.sob;
   a.O8 = (unsigned char*)d.O8; a.o8_scale = d.o8_scale; a.o8_amax = (unsigned int*)d.o8_amax;
   a.row_off = d.row_off; a.Tqd = d.Tq; a.Tkd = d.Tk;
-  a.lse = d.lse; a.klen = d.klen; a.B = d.B; a.H = d.H; a.Tq = d.Tq; a.Tk = d.Tk; a.hd = d.hd; a.Tqp = d.Tqp;
+  a.lse = d.lse; a.klen = d.klen; a.key_slot = d.key_slot; a.B = d.B; a.H = d.H; a.Tq = d.Tq; a.Tk = d.Tk; a.hd = d.hd; a.Tqp = d.Tqp;
   a.causal = d.causal; a.scale = d.scale;
   a.dO = (const unsigned short*)d.dO; a.lddo = d.lddo; a.sdob = d.sdob; a.Dq = d.Dq;
   a.dQ = (unsigned short*)d.dQ; a.dK = (unsigned short*)d.dK; a.dV = (unsigned short*)d.dV;
@@ -2119,6 +2141,23 @@ extern "C" int ca_attn_fwd(const CaAttnDesc* desc, void* stream) {
     AttnArgs as = a;
     unsigned sgrid;
     if (int rc = smallq_split(*desc, as, sgrid)) return rc;
+    if (desc->key_slot) {  // the same two kernels with the row's table of cache rows behind the rings
+      const int tab = (desc->Tk * 4 + 15) / 16 * 16;
+      static bool attr_ks = false;
+      if (!attr_ks) {
+        hipFuncSetAttribute((const void*)attn_fwd_smallq_kernel<64, false, 3, true>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, SMALLQ_LDS + 4096 * 4);
+        hipFuncSetAttribute((const void*)attn_fwd_smallq_kernel<64, false, 2, true>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, SMALLQ_LDS2 + 4096 * 4);
+        attr_ks = true;
+      }
+      if (sgrid >= smallq_two_per_cu())
+        hipLaunchKernelGGL((attn_fwd_smallq_kernel<64, false, 2, true>), dim3(sgrid), block, SMALLQ_LDS2 + tab, s, as);
+      else
+        hipLaunchKernelGGL((attn_fwd_smallq_kernel<64, false, 3, true>), dim3(sgrid), block, SMALLQ_LDS + tab, s, as);
+      CA_CHECK_LAUNCH("ca_attn_fwd");
+      return CA_OK;
+    }
     if (sgrid >= smallq_two_per_cu())
       hipLaunchKernelGGL((attn_fwd_smallq_kernel<64, false, 2>), dim3(sgrid), block, SMALLQ_LDS2, s, as);
     else
@@ -2139,7 +2178,8 @@ extern "C" int ca_decode_attn_qproj(const CaAttnDesc* desc, const void* x, int64
                                     const float* ln_beta, float ln_eps, const void* Wq, int64_t ldw, const float* bq,
                                     int32_t d_model, void* stream) {
   CA_CHECK_ARG(desc && x && ln_gamma && ln_beta && Wq && bq, "ca_decode_attn_qproj: null pointer");
-  CA_CHECK_ARG(desc->K && desc->V && desc->O && desc->B > 0 && desc->H > 0 && desc->Tk > 0 && !desc->row_off,
+  CA_CHECK_ARG(desc->K && desc->V && desc->O && desc->B > 0 && desc->H > 0 && desc->Tk > 0 && !desc->row_off &&
+                   !desc->key_slot,
                "ca_decode_attn_qproj: bad descriptor");
   CA_CHECK_ARG(desc->Tq == 1 && desc->hd <= 64 && (desc->hd % 8) == 0 && !desc->causal && desc->dropout_p == 0.f,
                "ca_decode_attn_qproj: one query per clip, head_dim <= 64, no mask, no dropout");
@@ -2181,6 +2221,7 @@ extern "C" int ca_attn_bwd(const CaAttnDesc* desc, void* stream) {
   if (int rc = attn_check(desc, "ca_attn_bwd")) return rc;
   CA_CHECK_ARG(desc->dO && desc->O && desc->Dq && desc->dQ && desc->dK && desc->dV, "ca_attn_bwd: null pointer");
   CA_CHECK_ARG((desc->lddo % 8) == 0, "ca_attn_bwd: lddo must be a multiple of 8");
+  CA_CHECK_ARG(desc->key_slot == nullptr, "ca_attn_bwd: key_slot is a forward (decode) option");
   const AttnArgs a = to_args(*desc);
   hipStream_t s = (hipStream_t)stream;
   static const int wide = [] { const char* e = getenv("CA_ATTN_WIDE"); return e ? atoi(e) : 1; }();

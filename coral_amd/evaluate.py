@@ -39,17 +39,26 @@ def transcribe(model, processor, arrays: list, batch_size: int = 16) -> list[str
     return out
 
 
-def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max_length: int | None = None):
+def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max_length: int | None = None,
+                       num_beams: int = 1):
     """The Whisper branch of the ASR pipeline ($TF/pipelines/automatic_speech_recognition.py:345,529,600): pad / trim
     every clip to 30 s, log-mel on the GPU, `model.generate(input_features, language="danish", task="transcribe")`
     (R/src/coral/evaluate.py:56-60), decode the generated ids without special tokens.
-    -> (texts, id rows).  Without the byte-level BPE files (offline) the texts are the ids rendered as words."""
+    -> (texts, id rows).  Without the byte-level BPE files (offline) the texts are the ids rendered as words.
+    num_beams >= 2: beam search (`generate_kwargs={"num_beams": k}` of the pipeline); a batch is then decoded at most
+    128 // num_beams clips at a time (the decoder's row limit)."""
     model.eval()
     texts, rows = [], []
     max_length = int(max_length or model.shape.max_target_positions)
+    num_beams = int(num_beams or 1)
+    if num_beams < 1:
+        raise ValueError(f"num_beams must be a positive integer, got {num_beams}")
+    gen_kw = dict(num_beams=num_beams) if num_beams > 1 else {}
+    if num_beams > 1:
+        batch_size = max(1, min(batch_size, 128 // num_beams))
     for i in range(0, len(arrays), batch_size):
         feats = processor.feature_extractor(arrays[i:i + batch_size], sampling_rate=processor.feature_extractor.sampling_rate)
-        ids = model.generate(feats, language="danish", task="transcribe", max_length=max_length)
+        ids = model.generate(feats, language="danish", task="transcribe", max_length=max_length, **gen_kw)
         ids = ids.tolist() if hasattr(ids, "tolist") else [list(map(int, r)) for r in ids]
         rows += ids
         texts += processor.batch_decode(ids, skip_special_tokens=True)
@@ -97,7 +106,7 @@ def evaluate(config, examples: list | None = None) -> dict:
                 w = np.clip(0.1 * rng.randn(n), -1, 1).astype(np.float32)
                 examples.append(dict(audio=w / np.abs(w).max(), text=""))
         preds, id_rows = transcribe_whisper(model, processor, [e["audio"] for e in examples], config.batch_size,
-                                            config.get("generation_max_length", None))
+                                            config.get("generation_max_length", None), config.get("num_beams", 1) or 1)
     else:
         if examples is None:
             examples = [dict(audio=ex["input_values"], text=ex["text"])

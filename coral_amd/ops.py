@@ -712,6 +712,22 @@ def argmax_advance(logits, suppress, out, rows, V, ldv, done, ids, tok, pos, kle
                                   _p(tok), _p(pos), _p(klen), int(pad_id), int(eos_id), _stream()), "ca_argmax_advance")
 
 
+def beam_select_workspace_bytes(B, k, V):
+    return lib().ca_beam_select_workspace_bytes(B, k, V)
+
+
+def beam_select(logits, suppress, run_score, B, k, V, ldv, cand_score, cand_parent, cand_token, ws):
+    """Whisper beam search: per clip the best 2k of the k x V candidates log_softmax(logits) + run_score (suppress as -inf
+    after the log-softmax), ranked by (score, beam * V + token) -> cand_score / cand_parent / cand_token [B, 2k]."""
+    check(lib().ca_beam_select(_p(logits), ldv, _p(suppress), _p(run_score), B, k, V, _p(cand_score), _p(cand_parent),
+                               _p(cand_token), _p(ws), ws.numel() * _ELT[ws.dtype], _stream()), "ca_beam_select")
+
+
+def beam_advance(desc):
+    """One step of beam bookkeeping on the device (`desc`: a filled _lib.CaBeamDesc whose tensors the caller keeps alive)."""
+    check(lib().ca_beam_advance(C.byref(desc), _stream()), "ca_beam_advance")
+
+
 def whisper_decode_token_supported(B, d, f, H, V) -> bool:
     """True when ca_whisper_decode_token (one persistent launch per decoded token) takes this shape on this device."""
     return bool(lib().ca_whisper_decode_token_supported(B, d, f, H, V))
@@ -755,8 +771,9 @@ def prof_end():
 
 def _attn_desc(Q, K, V, O, lse, *, B, H, Tq, Tk, hd, Tqp, scale, ldq, ldk, ldv, ldo, sqb, skb, svb, sob,
                q_off=0, k_off=0, v_off=0, o_off=0, klen=None, causal=False, dropout_p=0.0, dropout_seed=0,
-               O8=None, o8_scale=None, o8_amax=None, split_ws=None, row_off=None):
+               O8=None, o8_scale=None, o8_amax=None, split_ws=None, row_off=None, key_slot=None):
     d = CaAttnDesc()
+    d.key_slot = _p(key_slot)  # Tq = 1 decode form: int32 [B, Tk], the cache row of every key (beam search)
     d.row_off = _p(row_off)  # packed rows: utterance b at rows row_off[b] .. row_off[b + 1] (Tq = Tk = the longest)
     if split_ws is not None:  # key split of the small-query kernel (attn_split_workspace)
         d.split_ws, d.split_ws_bytes = _p(split_ws), split_ws.numel() * _ELT[split_ws.dtype]

@@ -15,6 +15,9 @@ added in the second conv's epilogue.  The encoder and decoder layers are the pre
 run on inference workspaces; the training engine (whisper_train.py) runs the same blocks, stem and head
 with saved activations.  Greedy decoding appends one token at a time against a self-attention K|V cache
 (decode_step, or the graph-replayed / persistent token step), the cross-attention K|V computed once per clip.
+Beam search (`generate(num_beams=k)`, `_generate_beam`): the launch-sequence step over clips x k rows, the K|V cache read
+through an ancestry table (CaAttnDesc.key_slot), candidates ranked and beams kept on the device (csrc/beam.hip), with the
+semantics of $TF/generation/utils.py:3208-3508 (GenerationMixin._beam_search).
 """
 
 from __future__ import annotations
@@ -155,6 +158,40 @@ def sinusoid_positions(length: int, channels: int, max_timescale: float = 10000.
     inv = torch.exp(-inc * torch.arange(channels // 2, dtype=torch.float32))
     t = torch.arange(length, dtype=torch.float32).view(-1, 1) * inv.view(1, -1)
     return torch.cat([t.sin(), t.cos()], dim=1)
+
+
+# generation arguments of transformers' `generate` that change what beam search returns and that this build does not
+# implement: refused by name, never swallowed (values that leave the search as it is - None, or the neutral value - pass)
+_BEAM_REFUSED = {"num_return_sequences": (None, 1), "do_sample": (None, False), "temperature": (None, 1.0), "top_k": (None,),
+                 "top_p": (None, 1.0), "typical_p": (None, 1.0), "num_beam_groups": (None, 1), "diversity_penalty": (None, 0.0),
+                 "repetition_penalty": (None, 1.0), "no_repeat_ngram_size": (None, 0), "penalty_alpha": (None,),
+                 "return_timestamps": (None, False), "low_memory": (None, False), "constraints": (None,),
+                 "force_words_ids": (None,), "bad_words_ids": (None,), "min_length": (None, 0), "min_new_tokens": (None,),
+                 "max_new_tokens": (None,), "logits_processor": (None,), "stopping_criteria": (None,),
+                 "prefix_allowed_tokens_fn": (None,), "assistant_model": (None,), "no_speech_threshold": (None,),
+                 "compression_ratio_threshold": (None,), "logprob_threshold": (None,), "prompt_ids": (None,),
+                 "return_dict_in_generate": (None, False), "output_scores": (None, False)}
+
+
+def check_beam_arguments(clips: int, num_beams, length_penalty, early_stopping, other: dict):
+    """The limits of generate(num_beams=k): raises ValueError for what the beam search here does not do."""
+    if not isinstance(num_beams, int) or isinstance(num_beams, bool) or num_beams < 1:
+        raise ValueError(f"num_beams must be a positive integer, got {num_beams!r}")
+    if num_beams > _lib.BEAM_MAX_BEAMS:
+        raise ValueError(f"num_beams={num_beams} exceeds the limit of {_lib.BEAM_MAX_BEAMS} beams")
+    if clips * num_beams > _lib.BEAM_MAX_ROWS:
+        raise ValueError(f"{clips} clips x num_beams={num_beams} = {clips * num_beams} decoder rows exceed the limit of "
+                         f"{_lib.BEAM_MAX_ROWS} (clips x num_beams <= {_lib.BEAM_MAX_ROWS}): decode fewer clips at a time")
+    if early_stopping not in (True, False):
+        raise ValueError(f"early_stopping={early_stopping!r} is not implemented (True and False are; \"never\" is not)")
+    if not isinstance(length_penalty, (int, float)) or isinstance(length_penalty, bool) or not math.isfinite(length_penalty):
+        raise ValueError(f"length_penalty must be a finite number, got {length_penalty!r}")
+    for name, val in other.items():
+        neutral = _BEAM_REFUSED.get(name)
+        if neutral is None:
+            raise ValueError(f"generate(num_beams={num_beams}): argument {name}={val!r} is not known to this build")
+        if not any(val is n or (n is not None and type(val) is type(n) and val == n) for n in neutral):
+            raise ValueError(f"generate(num_beams={num_beams}): {name}={val!r} is not implemented with beam search")
 
 
 class WhisperEngine:
@@ -647,10 +684,25 @@ class WhisperEngine:
         return out
 
     def generate(self, input_features, prefix: list[int], max_length: int, suppress_tokens=None,
-                 begin_suppress_tokens=None, use_cache: bool = True, use_graph: bool = True) -> list[list[int]]:
+                 begin_suppress_tokens=None, use_cache: bool = True, use_graph: bool = True, num_beams: int = 1,
+                 length_penalty: float = 1.0, early_stopping: bool = False, return_trace: bool = False,
+                 _beam_path: bool = False) -> list[list[int]]:
         """Greedy decoding with a forced prefix (<|sot|><|da|><|transcribe|><|notimestamps|> in CoRal's
-        evaluation): masked argmax on the GPU (ca_argmax_masked), stop at EOS / max_length."""
+        evaluation): masked argmax on the GPU (ca_argmax_masked), stop at EOS / max_length.
+        num_beams = k >= 2: beam search (`_generate_beam`; length_penalty, early_stopping True / False as in
+        transformers); return_trace=True then returns (ids, trace).  num_beams = 1 is the greedy code, untouched
+        (_beam_path=True routes it through the beam launches instead: a test switch)."""
         s, dev = self.s, self.device
+        beam = num_beams != 1 or _beam_path
+        if beam:
+            check_beam_arguments(int(input_features.shape[0]), num_beams, length_penalty, early_stopping, {})
+            if max_length <= len(prefix) or max_length > s.max_target_positions:
+                raise ValueError(f"beam search needs len(prefix) < max_length <= {s.max_target_positions}, got {max_length}")
+            if s.d_model // s.decoder_attention_heads > 64:
+                raise ValueError("beam search needs head_dim <= 64 (the single-query attention kernel reads the cache "
+                                 "through CaAttnDesc.key_slot)")
+        elif return_trace:
+            raise ValueError("return_trace is a beam search option (num_beams >= 2)")
         enc = self.encode(input_features)
         kv = self.cross_kv(enc)
         B = enc.shape[0]
@@ -661,6 +713,9 @@ class WhisperEngine:
         sup_begin = sup.clone()
         if begin_suppress_tokens:
             sup_begin[torch.tensor(list(begin_suppress_tokens), device=dev)] = 1
+        if beam:
+            return self._generate_beam(kv, prefix, max_length, sup, sup_begin, num_beams, float(length_penalty),
+                                       bool(early_stopping), return_trace, use_graph)
         if use_cache and use_graph and max_length > len(prefix) + 2:
             return self._generate_graph(kv, prefix, max_length, sup, sup_begin)
         ids = torch.tensor([prefix] * B, dtype=torch.int64, device=dev)
@@ -766,3 +821,162 @@ class WhisperEngine:
         if bool(allfin.any()):
             keep = int(torch.nonzero(allfin)[0]) + 1
         return out[:, :keep].tolist()
+
+    # ---- beam search ---------------------------------------------------------------------------------------------------
+    def _beam_state(self, B, k, Lmax, P, max_length, length_penalty, early_stopping, cross_kv):
+        """Device state of the beam search: like `_graph_state`, everything that changes between tokens lives in device
+        memory.  The ancestry table `anc` (the cache row that holds position t of beam row r: CaAttnDesc.key_slot) and
+        the running ids are double-buffered: step n reads buffer n & 1 and ca_beam_advance writes the other."""
+        s, dev = self.s, self.device
+        R, V, Vp = B * k, s.vocab_size, _r8(s.vocab_size)
+        i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=dev)  # noqa: E731
+        f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+        g = dict(B=B, k=k, tok=i32(R), pos=i32(R), klen=i32(R), run_score=f32(R), logits=f32(R, Vp),
+                 anc=[i32(R, Lmax), i32(R, Lmax)], ids=[i32(R, Lmax), i32(R, Lmax)],
+                 cand_score=f32(B, 2 * k), cand_parent=i32(B, 2 * k), cand_token=i32(B, 2 * k),
+                 fin_score=torch.full((R,), -1.0e9, dtype=torch.float32, device=dev), fin_len=i32(R), fin_seq=i32(R),
+                 fin_ids=i32(R, Lmax), fin_count=i32(B), heur=torch.ones(B, dtype=torch.int32, device=dev),
+                 done=torch.zeros(B, dtype=torch.bool, device=dev),
+                 tr_parent=i32(Lmax, B, k), tr_token=i32(Lmax, B, k), tr_score=f32(Lmax, B, k),
+                 len_pen=torch.tensor([float(n) ** length_penalty for n in range(Lmax + 1)], dtype=torch.float32).to(dev),
+                 select_ws=torch.zeros(ops.beam_select_workspace_bytes(B, k, V), dtype=torch.uint8, device=dev),
+                 # the cross-attention runs with B = clips and Tq = k: the key split is that of B x H items, as in greedy
+                 split=ops.attn_split_workspace(B, s.decoder_attention_heads, dev), cross=cross_kv)
+        g["desc"] = []
+        for par in (0, 1):
+            dsc = _lib.CaBeamDesc()
+            dsc.B, dsc.k, dsc.max_len, dsc.prompt_len, dsc.max_length = B, k, Lmax, P, max_length
+            dsc.eos_id, dsc.early_stopping = s.eos_token_id, int(early_stopping)
+            for n in ("len_pen", "cand_score", "cand_parent", "cand_token", "run_score", "tok", "pos", "klen", "fin_score",
+                      "fin_len", "fin_seq", "fin_ids", "fin_count", "heur", "done", "tr_parent", "tr_token", "tr_score"):
+                setattr(dsc, n, g[n].data_ptr())
+            dsc.anc_in, dsc.anc_out = g["anc"][par].data_ptr(), g["anc"][1 - par].data_ptr()
+            dsc.ids_in, dsc.ids_out = g["ids"][par].data_ptr(), g["ids"][1 - par].data_ptr()
+            g["desc"].append(dsc)
+        return g
+
+    def _beam_pick(self, g: dict, suppress: torch.Tensor, par: int):
+        """Rank the k x V continuations of every clip and take the step's decisions (tables: buffer par -> 1 - par)."""
+        V, Vp = self.s.vocab_size, _r8(self.s.vocab_size)
+        ops.beam_select(g["logits"], suppress, g["run_score"], g["B"], g["k"], V, Vp, g["cand_score"], g["cand_parent"],
+                        g["cand_token"], g["select_ws"])
+        ops.beam_advance(g["desc"][par])
+
+    def _beam_token_step(self, cache: dict, g: dict, suppress: torch.Tensor, par: int):
+        """`_token_step_launches` over clips x beams rows with three changes: the self-attention reads the K|V cache through
+        the ancestry table (rows are written once, by the beam slot that produced them, and never copied); the
+        cross-attention takes a clip's k beams as k queries against the clip's ONE encoder K|V; ca_beam_select +
+        ca_beam_advance stand where ca_argmax_advance stood."""
+        s, st = self.s, self.store
+        p32, p16, o = st.p32, st.p16, st.off
+        B, k, Lmax = g["B"], g["k"], cache["max_len"]
+        R = B * k
+        d, H, Te = s.d_model, s.decoder_attention_heads, s.max_source_positions
+        hd = d // H
+        w = self._decoder_ws(R, 1)
+        x, q, ctx, lse = w["ca"]["x"], w["ca"]["q"], w["ca"]["ctx"], w["ca"]["lse"]
+        h0, h1 = w["h"]
+        self._embed(g["tok"], g["pos"], h0, R)
+        ln_in = LN_IN_GEMM and R <= 128 and d <= 2048
+        for l, (_, _, ff) in enumerate(self.dec_blocks):
+            p = f"model.decoder.layers.{l}."
+            ckv = cache["kv"][l]
+            if not ln_in:
+                ops.layernorm_fwd(h0, st.view(p + "self_attn_layer_norm.weight"), st.view(p + "self_attn_layer_norm.bias"),
+                                  x, None, R, d, s.layer_norm_eps)
+            ops.gemm(h0 if ln_in else x, p16, q, M=R, N=3 * d, K=d, lda=d, ldb=d, ldc=d,
+                     b_off=o(p + "self_attn.q_proj.weight"),
+                     bias=p32, bias_off=o(p + "self_attn.q_proj.bias"), c_split_n=d, C_hi=ckv, ldc_hi=2 * d,
+                     c_row_index=g["pos"], c_row_mul=Lmax,
+                     a_ln=(st.view(p + "self_attn_layer_norm.weight"), st.view(p + "self_attn_layer_norm.bias"),
+                           s.layer_norm_eps) if ln_in else None)
+            ops.attn_fwd(q, ckv, ckv, ctx, lse, B=R, H=H, Tq=1, Tk=Lmax, hd=hd, Tqp=32,
+                         scale=hd ** -0.5, ldq=d, ldk=2 * d, ldv=2 * d, ldo=d, sqb=d, skb=Lmax * 2 * d,
+                         svb=Lmax * 2 * d, sob=d, k_off=0, v_off=d, klen=g["klen"], key_slot=g["anc"][par])
+            ops.gemm(ctx, p16, h1, M=R, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(p + "self_attn.out_proj.weight"),
+                     bias=p32, bias_off=o(p + "self_attn.out_proj.bias"), epilogue=EPI_RESIDUAL, R=h0, ldr=d)
+            if not ln_in:
+                ops.layernorm_fwd(h1, st.view(p + "encoder_attn_layer_norm.weight"), st.view(p + "encoder_attn_layer_norm.bias"),
+                                  x, None, R, d, s.layer_norm_eps)
+            ops.gemm(h1 if ln_in else x, p16, q, M=R, N=d, K=d, lda=d, ldb=d, ldc=d,
+                     b_off=o(p + "encoder_attn.q_proj.weight"), bias=p32, bias_off=o(p + "encoder_attn.q_proj.bias"),
+                     a_ln=(st.view(p + "encoder_attn_layer_norm.weight"), st.view(p + "encoder_attn_layer_norm.bias"),
+                           s.layer_norm_eps) if ln_in else None)
+            ops.attn_fwd(q, g["cross"][l], g["cross"][l], ctx, lse, B=B, H=H, Tq=k, Tk=Te, hd=hd, Tqp=32,
+                         scale=hd ** -0.5, ldq=d, ldk=2 * d, ldv=2 * d, ldo=d, sqb=k * d, skb=Te * 2 * d,
+                         svb=Te * 2 * d, sob=k * d, k_off=0, v_off=d, split_ws=g["split"])
+            ops.gemm(ctx, p16, h0, M=R, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(p + "encoder_attn.out_proj.weight"),
+                     bias=p32, bias_off=o(p + "encoder_attn.out_proj.bias"), epilogue=EPI_RESIDUAL, R=h1, ldr=d)
+            ff.forward(h0, h1, w["ff"], R)
+            h0, h1 = h1, h0
+        self._head(h0, w["hf"], R, logits=g["logits"])
+        self._beam_pick(g, suppress, par)
+
+    def _generate_beam(self, kv, prefix, max_length, sup, sup_begin, k, length_penalty, early_stopping, return_trace,
+                       use_graph=True):
+        """Beam search as GenerationMixin._beam_search states it ($TF/generation/utils.py:3208-3508; restated in
+        tests/whisper_beam_ref.py), on the launch-sequence path.  The forced prefix runs once per clip into beam slot 0;
+        the ancestry table makes it visible to all k slots.  The token step is captured once per table parity and
+        replayed; the host looks at the per-clip done flags every 8 tokens, as greedy does.  The ids of the running and
+        the finished hypotheses are kept on the device as [clips x k, max_length] tables that ca_beam_advance re-gathers
+        with the ancestry rows (the same few KB per step): a finished hypothesis needs its ids at the moment it finishes,
+        when its beam may not survive the step, so back-pointers alone would have to keep every step's parents and be
+        walked at the end for nothing saved."""
+        s, dev = self.s, self.device
+        d, Te = s.d_model, s.max_source_positions
+        B, V, Vp, P = kv[0].shape[0] // (Te * 2 * d), s.vocab_size, _r8(s.vocab_size), len(prefix)
+        R, Lmax = B * k, max_length
+        cache = self.new_decode_cache(R, Lmax)
+        g = self._beam_state(B, k, Lmax, P, max_length, length_penalty, early_stopping, kv)
+        # the forced prefix, eagerly, on B rows: clip b's K|V go to cache row b * k (beam slot 0 of the clip)
+        ids0 = torch.tensor([prefix] * B, dtype=torch.int64, device=dev)
+        base = self.decode_step(ids0, kv, dict(kv=cache["kv"], max_len=k * Lmax, pos=0, B=B))
+        g["logits"].view(B, k, Vp)[:, :, :V] = base[:, None, :]
+        slot0 = (torch.arange(R, device=dev, dtype=torch.int32) // k) * k
+        g["anc"][0][:, :P] = slot0[:, None]  # no copy: every beam's prefix positions name the clip's slot 0
+        g["ids"][0][:, :P] = ids0[0].to(torch.int32)
+        g["run_score"].view(B, k)[:, 1:] = -1.0e9  # the first step expands one beam ($TF/generation/utils.py:3332-3333)
+        g["pos"].fill_(P - 1)
+        g["klen"].fill_(P)
+        self._beam_pick(g, sup_begin, 0)  # the first free position: begin-suppress set
+        n_done, par = P + 1, 1
+        if n_done < max_length and not bool(g["done"].all()):
+            self._beam_token_step(cache, g, sup, par)  # eager warm-up of the captured sequence
+            n_done, par = n_done + 1, par ^ 1
+        graphs = {}
+
+        def replay(par):
+            if not use_graph:
+                return self._beam_token_step(cache, g, sup, par)
+            if par not in graphs:
+                torch.cuda.synchronize()
+                graphs[par] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[par]):
+                    self._beam_token_step(cache, g, sup, par)
+            graphs[par].replay()
+
+        while n_done < max_length:
+            if (n_done - P) % 8 == 2 and bool(g["done"].all()):  # host check every 8 tokens
+                break
+            replay(par)
+            n_done, par = n_done + 1, par ^ 1
+        # the best finished hypothesis of every clip: highest score, of equal scores the one that entered first
+        fs, fl = g["fin_score"].view(B, k).cpu(), g["fin_len"].view(B, k).cpu()
+        fq, fi = g["fin_seq"].view(B, k).cpu(), g["fin_ids"].view(B, k, Lmax).cpu()
+        out, best = [], []
+        for b in range(B):
+            live = [j for j in range(k) if int(fl[b, j]) > 0]
+            if not live:
+                raise ops.CoralAmdError("beam search ended without a finished hypothesis")
+            j = min(live, key=lambda j: (-float(fs[b, j]), int(fq[b, j])))
+            best.append(j)
+            out.append(fi[b, j, :int(fl[b, j])].tolist())
+        n = max(len(r) for r in out)
+        out = [r + [s.pad_token_id] * (n - len(r)) for r in out]
+        if not return_trace:
+            return out
+        steps = n_done - P
+        trace = dict(parent=g["tr_parent"][:steps].cpu(), token=g["tr_token"][:steps].cpu(), score=g["tr_score"][:steps].cpu(),
+                     fin_score=fs, fin_len=fl, fin_seq=fq, fin_ids=fi, best=best, steps=steps,
+                     sequence_scores=[float(fs[b, j]) for b, j in enumerate(best)])
+        return out, trace

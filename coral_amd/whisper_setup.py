@@ -192,13 +192,23 @@ class WhisperForConditionalGeneration:
     def backward(self, **kw):
         return self.engine.backward(**kw)
 
-    def generate(self, input_features, language="danish", task="transcribe", max_length: int = 225, **_):
+    def generate(self, input_features, language="danish", task="transcribe", max_length: int = 225, num_beams: int | None = 1,
+                 length_penalty: float = 1.0, early_stopping=False, **other):
+        """Greedy (num_beams 1 / None: other keyword arguments are ignored, as before) or beam search (num_beams >= 2,
+        transformers' semantics; every generation argument this build does not implement is then refused by name)."""
         if language not in ("danish", "da") or task != "transcribe":
             raise ValueError("only language='danish', task='transcribe' (CoRal's evaluation call) is wired up")
         prefix = prefix_ids(self.shape)
+        num_beams = 1 if num_beams is None else num_beams
+        kw = {}
+        if num_beams != 1:
+            from .whisper import check_beam_arguments
+
+            check_beam_arguments(int(input_features.shape[0]), num_beams, length_penalty, early_stopping, other)
+            kw = dict(num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping)
         # CoRal clears `suppress_tokens`; the default begin-suppress set (blank ' ' = 220, eos) stays
         return self.engine.generate(input_features, prefix, max_length, suppress_tokens=None,
-                                    begin_suppress_tokens=[220, self.shape.eos_token_id])
+                                    begin_suppress_tokens=[220, self.shape.eos_token_id], **kw)
 
 
 class WhisperModelSetup(ModelSetup):

@@ -392,6 +392,12 @@ typedef struct CaAttnDesc {
   float* lse;
   float* Dq;
   const int32_t* klen;
+  /* Optional, forward only, the single-query decode form (Tq = 1, klen set, head_dim <= 64, no causal mask, dropout,
+   * O8, split_ws or row_off; anything else is CA_ERR_ARG): int32 [B, Tk] on the device.  Key and value t of query row r
+   * are read from cache row key_slot[r * Tk + t] (0 <= slot < B) at position t - K + slot * skb + t * ldk - instead of
+   * from row r: beam search reorders its hypotheses by rewriting this table, the K|V rows stay where the beam slot
+   * that produced them wrote them.  Entries at t >= klen[r] are not read.  NULL = off (every row reads its own). */
+  const int32_t* key_slot;
   int64_t ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;
   int64_t sqb, skb, svb, sob, sdob, sdqb, sdkb, sdvb;
   int32_t B, H, Tq, Tk, hd, Tqp, causal;
@@ -443,6 +449,59 @@ int ca_attn_bwd(const CaAttnDesc* desc, void* stream);
 int ca_decode_attn_qproj(const CaAttnDesc* desc, const void* x, int64_t ldx, const float* ln_gamma,
                          const float* ln_beta, float ln_eps, const void* Wq, int64_t ldw, const float* bq,
                          int32_t d_model, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Whisper beam search (csrc/beam.hip): GenerationMixin._beam_search of $TF/generation/utils.py:3208-3508 with
+ * every value that changes between tokens in device memory.  Order everywhere: higher score first, then the lower
+ * flat index beam * V + token.  Limits: num_beams <= CA_BEAM_MAX_BEAMS, clips x num_beams <= CA_BEAM_MAX_ROWS.
+ *
+ * ca_beam_select: logits fp32 [B*k, ldv] (row b*k + j = beam j of clip b, first V columns valid), suppress u8 [V]
+ * (1 = masked to -inf AFTER the log-softmax; NULL = none), run_score fp32 [B*k].  Per clip the best 2k of the k x V
+ * candidates log_softmax(logits)[j, t] + run_score[j], best first: cand_score fp32 / cand_parent int32 (0..k-1) /
+ * cand_token int32, each [B, 2k] (a clip with fewer than 2k unmasked candidates gets score -inf, token -1).  The
+ * logits are read once: chunk maxima, sums of exp and partial top-2k lists in one pass, merged per row and per clip.
+ * ws: ca_beam_select_workspace_bytes(B, k, V) bytes, 16-byte aligned.  Deterministic (no atomics).
+ *
+ * ca_beam_advance: one step's bookkeeping from the ranked candidates, in one launch.  cur = pos[b*k] + 1 tokens are
+ * in every running sequence.  A candidate "hits" when its token is eos_id or cur + 1 == max_length.  The best k by
+ * score + (hit ? -1e9 : 0) become the running beams: run_score, tok, pos (+1), klen (+1), and the table rows
+ * anc_out[j, :cur] = anc_in[parent_j, :cur], anc_out[j, cur] = b*k + j (the cache row that will hold position cur of
+ * beam j: CaAttnDesc.key_slot), ids_out likewise with the token.  Hits among the first k ranks enter the clip's table
+ * of finished hypotheses with score cand_score / len_pen[cur + 1 - prompt_len] while the clip is open (heur[b] set and
+ * not (early_stopping and table full)): an empty slot, or the worst entry's if the new score is higher.  fin_len = 0
+ * marks an empty slot, fin_seq the order of entry (equal scores: the earlier one ranks first).  Then heur[b] &=
+ * run_score[b, 0] / len_pen[cur + 1 - prompt_len] > (table full ? its lowest score : -1e9), and done[b] = !heur[b] or
+ * (early_stopping and full) or the last step.  tr_* (all or none): [max_len, B, k] trace of (parent, token, running
+ * score) at row cur - prompt_len.
+ * ---------------------------------------------------------------------------------- */
+#define CA_BEAM_MAX_BEAMS 16
+#define CA_BEAM_MAX_ROWS 128
+typedef struct CaBeamDesc {
+  int32_t B, k, max_len, prompt_len, max_length, eos_id, early_stopping;
+  const float* len_pen;      /* [max_len + 1]: n ** length_penalty */
+  const float* cand_score;   /* [B, 2k] from ca_beam_select */
+  const int32_t* cand_parent;
+  const int32_t* cand_token;
+  float* run_score;          /* [B*k] */
+  int32_t *tok, *pos, *klen; /* [B*k] */
+  const int32_t* anc_in;     /* [B*k, max_len] */
+  int32_t* anc_out;
+  const int32_t* ids_in;     /* [B*k, max_len] */
+  int32_t* ids_out;
+  float* fin_score;          /* [B*k] */
+  int32_t *fin_len, *fin_seq;
+  int32_t* fin_ids;          /* [B*k, max_len] */
+  int32_t* fin_count;        /* [B] hypotheses entered so far */
+  int32_t* heur;             /* [B] 1 while a running beam may still beat the finished ones */
+  uint8_t* done;             /* [B] */
+  int32_t *tr_parent, *tr_token;
+  float* tr_score;
+} CaBeamDesc;
+int64_t ca_beam_select_workspace_bytes(int32_t B, int32_t k, int32_t V);
+int ca_beam_select(const float* logits, int64_t ldv, const uint8_t* suppress, const float* run_score, int32_t B,
+                   int32_t k, int32_t V, float* cand_score, int32_t* cand_parent, int32_t* cand_token, void* ws,
+                   int64_t ws_bytes, void* stream);
+int ca_beam_advance(const CaBeamDesc* desc, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * CTC head: log_softmax(fp32) + CTC loss (+ gradient wrt logits) + greedy decode.

@@ -11,7 +11,7 @@ Weights: no checkpoints exist offline, so every parameter is overwritten with
 oracle.wav2vec2_ref.synth_params (name-keyed seeded values) — the tests regenerate the same
 weights instead of storing them.
 
-usage: python tools/gen_goldens.py [w2v2_tiny ctc featext tokenizer w2v2_cfg1 logmel whisper_tiny whisper_mid hf_ckpt trainer_traj]
+usage: python tools/gen_goldens.py [w2v2_tiny ctc featext tokenizer w2v2_cfg1 logmel whisper_tiny whisper_mid whisper_beam hf_ckpt trainer_traj]
 """
 
 from __future__ import annotations
@@ -462,6 +462,72 @@ def gen_whisper_mid():
     out["greedy_ids"] = ids.numpy()
     np.savez_compressed(GOLD / "whisper_mid.npz", **out)
     print("whisper_mid: loss", out["loss"], "greedy", ids.tolist())
+
+
+WHISPER_BEAM_FIXTURES = {
+    # name: (architecture, feature seed, forced prefix, suppress, begin-suppress): the whisper_tiny / whisper_mid fixtures
+    "tiny": (dict(d_model=64, encoder_layers=2, decoder_layers=2, encoder_attention_heads=4, decoder_attention_heads=4,
+                  encoder_ffn_dim=128, decoder_ffn_dim=128, num_mel_bins=80, vocab_size=200, max_target_positions=64,
+                  pad_token_id=150, decoder_start_token_id=151, eos_token_id=150),
+             9, [151, 160, 161, 162], [170, 171], [20, 150]),
+    "mid": (dict(d_model=512, encoder_layers=6, decoder_layers=6, encoder_attention_heads=8, decoder_attention_heads=8,
+                 encoder_ffn_dim=2048, decoder_ffn_dim=2048, num_mel_bins=80, vocab_size=2000, max_target_positions=64,
+                 pad_token_id=1950, decoder_start_token_id=1951, eos_token_id=1950),
+            11, [1951, 1960, 1961, 1962], [1970, 1971], [20, 1950]),
+}
+# The seeded random weights never rank their EOS among a step's best 2k, so the fixtures above only ever finish at
+# max_length.  The same weights and inputs with a frequent token declared EOS (a generation setting, no weight changes)
+# exercise finished hypotheses of different lengths, the length penalty and both early_stopping rules.
+for _n, _eos in (("tiny", 18), ("mid", 795)):
+    _kw, *_rest = WHISPER_BEAM_FIXTURES[_n]
+    WHISPER_BEAM_FIXTURES[f"{_n}_eos{_eos}"] = (dict(_kw, eos_token_id=_eos), *_rest)
+# (num_beams, length_penalty, early_stopping)
+WHISPER_BEAM_CASES = [(2, 1.0, False), (5, 1.0, False), (5, 1.0, True), (5, 0.6, False), (2, 0.6, True)]
+WHISPER_BEAM_MAX_LENGTH = 24
+
+
+def gen_whisper_beam():
+    """Beam search of transformers itself (GenerationMixin.generate -> _beam_search, $TF/generation/utils.py:3208) over the
+    whisper_tiny and whisper_mid fixtures' weights and inputs, with the forced prefix and the two suppress processors of
+    the greedy fixtures: ids and sequence scores per (num_beams, length_penalty, early_stopping)."""
+    from transformers import WhisperConfig, WhisperForConditionalGeneration
+    from transformers.generation import GenerationMixin
+    from transformers.generation.logits_process import (LogitsProcessorList, SuppressTokensAtBeginLogitsProcessor,
+                                                        SuppressTokensLogitsProcessor)
+
+    from oracle import whisper_ref as wref
+
+    out = {}
+    for name, (kw, seed, prefix, sup, sup_begin) in WHISPER_BEAM_FIXTURES.items():
+        c = wref.WhisperConfig(**kw)
+        hc = WhisperConfig(**{k: v for k, v in kw.items()}, max_source_positions=1500, bos_token_id=kw["pad_token_id"],
+                           dropout=0.0, attention_dropout=0.0, activation_dropout=0.0, encoder_layerdrop=0.0,
+                           decoder_layerdrop=0.0, apply_spec_augment=False, attn_implementation="eager",
+                           suppress_tokens=[], begin_suppress_tokens=[])
+        model = WhisperForConditionalGeneration(hc)
+        sd = model.state_dict()
+        with torch.no_grad():
+            for k, v in wref.synth_params(c).items():
+                sd[k].copy_(v)
+        model.eval()
+        model.generation_config.forced_decoder_ids = None
+        g = torch.Generator().manual_seed(seed)
+        feats = torch.randn(2, 80, 3000, generator=g) * 0.5
+        dec = torch.tensor([prefix] * 2)
+        for nb, lp, es in WHISPER_BEAM_CASES:
+            procs = LogitsProcessorList([SuppressTokensLogitsProcessor(sup),
+                                         SuppressTokensAtBeginLogitsProcessor(sup_begin, begin_index=len(prefix))])
+            with torch.no_grad():
+                res = GenerationMixin.generate(model, input_features=feats, decoder_input_ids=dec, num_beams=nb,
+                                               length_penalty=lp, early_stopping=es, do_sample=False,
+                                               max_length=WHISPER_BEAM_MAX_LENGTH, logits_processor=procs,
+                                               return_dict_in_generate=True, output_scores=True, use_cache=True)
+            key = f"{name}:k{nb}:lp{lp}:es{int(es)}"
+            out[key + ":ids"] = res.sequences.numpy()
+            out[key + ":scores"] = res.sequences_scores.numpy()
+            print("whisper_beam", key, res.sequences.tolist(), res.sequences_scores.tolist())
+    np.savez_compressed(GOLD / "whisper_beam.npz", **out)
+    print("whisper_beam.npz", (GOLD / "whisper_beam.npz").stat().st_size, "bytes")
 
 
 TINY_CKPT_W2V2 = dict(hidden_size=64, num_hidden_layers=2, num_attention_heads=4, intermediate_size=128,

@@ -163,6 +163,7 @@ class CaBeamDesc(C.Structure):
 
 BEAM_MAX_BEAMS, BEAM_MAX_ROWS = 16, 128  # CA_BEAM_MAX_BEAMS, CA_BEAM_MAX_ROWS
 FP8_GROUP_MAX = 8  # CA_FP8_GROUP_MAX
+CTC_COLLAPSE_TILE = 4096  # CA_CTC_COLLAPSE_TILE
 KMAJOR, MNMAJOR = 0, 1
 EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_DGELU, EPI_GELU_RESIDUAL = 0, 1, 2, 3, 4
 
@@ -242,6 +243,9 @@ SIGNATURES = {
         C.c_int,
         [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _vp],
     ),
+    "ca_ctc_stitch": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _i32, _vp]),
+    "ca_ctc_collapse_workspace_bytes": (_i64, [_i32, _i32]),
+    "ca_ctc_collapse_offsets": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     "ca_ctc_beam_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "ca_ctc_beam_decode": (C.c_int, [C.POINTER(CaCtcBeamDesc), _vp]),
     "ca_beam_select_workspace_bytes": (_i64, [_i32, _i32, _i32]),

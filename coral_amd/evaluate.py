@@ -9,10 +9,12 @@ from __future__ import annotations
 
 import csv
 import logging
+import math
 from pathlib import Path
 
 import torch
 
+from . import ops
 from .data import synthetic_examples
 from .metrics import cer, wer
 from .model_setup import load_model_setup
@@ -20,9 +22,23 @@ from .model_setup import load_model_setup
 logger = logging.getLogger(__package__)
 
 
-def transcribe(model, processor, arrays: list, batch_size: int = 16) -> list[str]:
+def transcribe(model, processor, arrays: list, batch_size: int = 16, chunk_length_s: float = 0, stride_length_s=None,
+               return_timestamps=None):
     """ASR-pipeline equivalent ($TF/pipelines/automatic_speech_recognition.py:345,569-575,679):
-    feature-extract, forward, argmax over all frames, CTC collapse, decode."""
+    feature-extract, forward, argmax over all frames, CTC collapse, decode.  -> list of texts.
+    chunk_length_s > 0: overlapping chunks with the pipeline's `chunk_length_s` / `stride_length_s` semantics
+    (coral_amd/longform.py); 0: every clip whole.  return_timestamps="char" | "word": a list of {"text", "chunks":
+    [{"text", "timestamp": (start_s, stop_s)}]} instead (greedy decoding only).  A whole clip of more than 4096 frames
+    (81.9 s), or one decoded with timestamps, is collapsed by `ca_ctc_collapse_offsets`."""
+    from .longform import check_timestamp_mode, collapse_rows, decode_rows, transcribe_long
+
+    with_lm = getattr(processor, "lm", None) is not None
+    check_timestamp_mode(return_timestamps, with_lm)
+    if chunk_length_s is not None and chunk_length_s < 0:
+        raise ValueError(f"chunk_length_s must be 0 (whole clips) or positive, got {chunk_length_s}")
+    if chunk_length_s:
+        res = transcribe_long(model, processor, arrays, chunk_length_s, stride_length_s, batch_size, return_timestamps)
+        return res if return_timestamps is not None else [r["text"] for r in res]
     model.eval()
     out = []
     for i in range(0, len(arrays), batch_size):
@@ -30,11 +46,24 @@ def transcribe(model, processor, arrays: list, batch_size: int = 16) -> list[str
         batch = processor.feature_extractor.pad(feats, padding="longest")
         with torch.no_grad():
             model(torch.from_numpy(batch["input_values"]), torch.from_numpy(batch["attention_mask"]))
-        if getattr(processor, "lm", None) is not None:  # Wav2Vec2ProcessorWithLM: LM-fused beam search on the GPU
-            ids, _ = model.engine.beam_decode(processor.device_tables(model.engine.device), tokenizer=processor.tokenizer,
-                                              **processor.decoder_params)
+        eng = model.engine
+        T = eng._saved["w"]["T"]
+        if with_lm:  # Wav2Vec2ProcessorWithLM: LM-fused beam search on the GPU
+            ids, _ = eng.beam_decode(processor.device_tables(eng.device), tokenizer=processor.tokenizer,
+                                     **processor.decoder_params)
+        elif T > 4096 or return_timestamps is not None:
+            # every frame of the padded batch, as the greedy kernel below decodes them: identity segments
+            w, B, s = eng._saved["w"], eng._saved["B"], eng.s
+            seg = torch.tensor([(b, 0, 0, T) for b in range(B)], dtype=torch.int32).to(eng.device)
+            raw = torch.empty(B, T, dtype=torch.int32, device=eng.device)
+            ops.ctc_stitch(w["logits"], seg, raw, None, B, T, s.vocab_size, w["Vp"], B, T)
+            sr = processor.feature_extractor.sampling_rate
+            res = decode_rows(collapse_rows(raw, None, s.pad_token_id), processor.tokenizer, return_timestamps,
+                              math.prod(s.conv_stride), sr)
+            out += res if return_timestamps is not None else [r["text"] for r in res]
+            continue
         else:
-            ids, _ = model.engine.greedy_decode()
+            ids, _ = eng.greedy_decode()
         out += [processor.tokenizer.decode(r, group_tokens=False) for r in ids]
     return out
 
@@ -87,6 +116,10 @@ def evaluate(config, examples: list | None = None) -> dict:
 
     model_dir = config.get("model_dir", config.model_id)
     mtype = saved_model_type(model_dir)
+    chunk_length_s = config.get("chunk_length_s", 0) or 0
+    if mtype == "whisper" and chunk_length_s > 0:
+        raise ValueError("chunk_length_s > 0 is built for wav2vec2 models only (Whisper long-form decoding is not): "
+                         "set chunk_length_s to 0")
     mcfg = DictConfig(model=DictConfig(type=mtype, sampling_rate=config.sampling_rate, decoder=None),
                       model_dir=model_dir, padding="longest",
                       max_seconds_per_example=config.max_seconds_per_example)
@@ -112,7 +145,8 @@ def evaluate(config, examples: list | None = None) -> dict:
             examples = [dict(audio=ex["input_values"], text=ex["text"])
                         for ex in synthetic_examples(processor, 2 * config.batch_size, 99, config.min_seconds_per_example,
                                                      min(3.0, config.max_seconds_per_example), config.sampling_rate)]
-        preds = transcribe(model, processor, [e["audio"] for e in examples], config.batch_size)
+        preds = transcribe(model, processor, [e["audio"] for e in examples], config.batch_size,
+                           chunk_length_s=chunk_length_s, stride_length_s=config.get("stride_length_s", None))
     preds = [p.lower().strip() for p in preds]
     labels = [e["text"].lower().strip() if config.lower_case else e["text"].strip() for e in examples]
     scores = dict(model_type=mtype, n=len(examples))

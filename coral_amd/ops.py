@@ -532,6 +532,23 @@ def ctc_greedy_decode(logits, in_len, raw, ids, out_len, B, T, V, ldv, blank):
                                      V, ldv, blank, _stream()), "ca_ctc_greedy_decode")
 
 
+def ctc_stitch(logits, seg, raw_out, logits_out, C_, T, V, ldv, R, Tout):
+    """Kept frames of C_ chunk logits [C_, T, ldv] -> raw_out int32 [R, Tout] (argmax) and, unless None, logits_out fp32
+    [R, Tout, ldv]; seg int32 [C_, 4] on the device = (row, frame offset, first kept frame, kept frames)."""
+    check(lib().ca_ctc_stitch(_p(logits), _p(seg), _p(raw_out), _p(logits_out), C_, T, V, ldv, R, Tout, _stream()),
+          "ca_ctc_stitch")
+
+
+def ctc_collapse_workspace_bytes(B, T):
+    return lib().ca_ctc_collapse_workspace_bytes(B, T)
+
+
+def ctc_collapse_offsets(raw, in_len, ids, start, end, out_len, ws, B, T, blank):
+    """CTC collapse of raw int32 [B, T] (any T) with the frame offsets of every emitted token (ca_ctc_collapse_offsets)."""
+    check(lib().ca_ctc_collapse_offsets(_p(raw), _p(in_len), _p(ids), _p(start), _p(end), _p(out_len), _p(ws),
+                                        ws.numel() * _ELT[ws.dtype], B, T, blank, _stream()), "ca_ctc_collapse_offsets")
+
+
 def ctc_beam_workspace_bytes(B, T, V, beam_width):
     return lib().ca_ctc_beam_workspace_bytes(B, T, V, beam_width)
 

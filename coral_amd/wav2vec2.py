@@ -892,19 +892,29 @@ class Wav2Vec2CTCEngine:
         ids_c, olen_c = ids.cpu(), olen.cpu()
         return [ids_c[b, :int(olen_c[b])].tolist() for b in range(B)], raw
 
-    def beam_decode(self, lm=None, beam_width: int = 100, in_len=None, tokenizer=None, **params):
+    def beam_decode(self, lm=None, beam_width: int = 100, in_len=None, tokenizer=None, logits=None, **params):
         """CTC prefix beam search on the logits of the last forward, fused with the n-gram LM `lm` (the device-table
         dict of `NGramLM.device_tables`, or an `NGramLM` together with `tokenizer`; None: no LM, for which
         alpha = beta = 0 is the plain CTC prefix beam search).  `params`: alpha, beta, unk_score_offset,
         token_min_logp, beam_prune_logp, score_boundary (defaults: coral_amd/ngram.py).  `tokenizer` names the word
         delimiter and the ids that are never emitted (<s>, </s>, <unk>); without it there are no word boundaries and
-        nothing is forbidden.  -> (ids list per row, scores fp32 [B] = S(y))."""
+        nothing is forbidden.  `logits`: a contiguous fp32 device tensor [B, T, ld >= V] to decode instead of the last
+        forward's (the stitched rows of coral_amd/longform.py).
+        -> (ids list per row, scores fp32 [B] = S(y))."""
         from .ngram import DEFAULT_PARAMS
 
-        sv = self._saved
-        w = sv["w"]
-        B, T, V, Vp = sv["B"], w["T"], self.s.vocab_size, w["Vp"]
+        V = self.s.vocab_size
         dev = self.device
+        if logits is None:
+            sv = self._saved
+            w = sv["w"]
+            B, T, Vp = sv["B"], w["T"], w["Vp"]
+            logits = w["logits"]
+        else:
+            if (logits.dim() != 3 or logits.dtype != torch.float32 or not logits.is_contiguous() or logits.shape[2] < V
+                    or not logits.is_cuda):
+                raise ValueError("beam_decode: logits must be a contiguous fp32 [B, T, ld >= V] tensor on the engine's device")
+            B, T, Vp = logits.shape
         blank = self.s.pad_token_id
         if tokenizer is not None:
             delim = tokenizer.vocab[tokenizer.word_delimiter_token]
@@ -929,7 +939,7 @@ class Wav2Vec2CTCEngine:
         olen = torch.empty(B, dtype=torch.int32, device=dev)
         score = torch.empty(B, dtype=torch.float32, device=dev)
         ws = torch.empty(ops.ctc_beam_workspace_bytes(B, T, V, beam_width), dtype=torch.uint8, device=dev)
-        ops.ctc_beam_decode(w["logits"], in_len, ids, olen, score, ws, B, T, V, Vp, blank, delim, forbidden.to(dev), lm,
+        ops.ctc_beam_decode(logits, in_len, ids, olen, score, ws, B, T, V, Vp, blank, delim, forbidden.to(dev), lm,
                             beam_width=beam_width, **p)
         ids_c, olen_c = ids.cpu(), olen.cpu()
         return [ids_c[b, :int(olen_c[b])].tolist() for b in range(B)], score

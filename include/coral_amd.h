@@ -524,6 +524,31 @@ int ca_ctc_greedy_decode(const float* logits, const int32_t* in_len, int32_t* ra
                          int64_t ldv, int32_t blank, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Long-form CTC transcription (coral_amd/longform.py; the chunked CTC branch of
+ * $TF/pipelines/automatic_speech_recognition.py: `items[:, left:right_n]` + concatenate, and the character offsets of
+ * $TF/models/wav2vec2/tokenization_wav2vec2.py: _compute_offsets).
+ * ca_ctc_stitch: logits fp32 [C,T,ldv] of a batch of chunks (first V columns valid); seg int32 [C,4] on the device =
+ *   (destination row, destination frame offset, first kept frame, number of kept frames; 0 = the chunk gives nothing).
+ *   raw_out int32 [R,Tout]: raw_out[row, off + j] = argmax of kept frame j (first maximum, as ca_ctc_greedy_decode);
+ *   logits_out fp32 [R,Tout,ldv] or NULL: the frame's ldv floats beside it.  Frames outside [off, off + keep) of a row
+ *   are not written, so a row fills up over several calls; a frame that would fall outside the chunk or the
+ *   destination is skipped.  16-byte loads / stores when ldv % 4 == 0 and the buffers are 16-byte aligned.
+ * ca_ctc_collapse_offsets: raw int32 [B,T] -> the CTC collapse of the first in_len[b] frames (NULL: T) of every row:
+ *   ids int32 [B,T] = the ids of the non-blank runs, start / end int32 [B,T] = a run's first frame and the first frame
+ *   behind it (the last run ends at in_len), all three padded with -1 behind out_len int32 [B].  ids and out_len are
+ *   those of ca_ctc_greedy_decode where that accepts T.  Any T < 2^31 - CA_CTC_COLLAPSE_TILE: a row is scanned in tiles
+ *   of CA_CTC_COLLAPSE_TILE frames by three launches (tile counts, scan of the tile counts, scatter), deterministic.
+ *   ws: ca_ctc_collapse_workspace_bytes(B, T) bytes.
+ * ---------------------------------------------------------------------------------- */
+#define CA_CTC_COLLAPSE_TILE 4096
+int ca_ctc_stitch(const float* logits, const int32_t* seg, int32_t* raw_out, float* logits_out, int32_t C, int32_t T,
+                  int32_t V, int64_t ldv, int32_t R, int32_t Tout, void* stream);
+int64_t ca_ctc_collapse_workspace_bytes(int32_t B, int32_t T);
+int ca_ctc_collapse_offsets(const int32_t* raw, const int32_t* in_len, int32_t* ids, int32_t* start, int32_t* end,
+                            int32_t* out_len, void* ws, int64_t ws_bytes, int32_t B, int32_t T, int32_t blank,
+                            void* stream);
+
+/* ------------------------------------------------------------------------------------
  * CTC prefix beam search with n-gram LM fusion (evaluation with `no_lm: false`; the reference decodes through
  * pyctcdecode, R/src/coral/wav2vec2.py:269-279 - this is the project's own decoder, parity with pyctcdecode is not
  * pinned).  Objective and search rules: header comment of coral_amd/csrc/ctc_beam.hip and DESIGN.md §8.

@@ -12,17 +12,14 @@
 //     transpose), so NT / NN / TN / TT all run natively without transposed copies.
 //   * out-of-range rows are clamped (results discarded), out-of-range k reads a zero page.
 #include "common.h"
+#include "gemm_plan.h"  // tile shapes, LDS sizes, the tile-grid arithmetic and the kernel-choice rule
 #include <type_traits>
 #include <cstdlib>
 
-#define BM 128
-#define BN 128
-#define BK 64
 #define TILE_BYTES (BM * BK * 2)  // 16 KiB per operand tile
 #define STAGE_BYTES (2 * TILE_BYTES)
 #define NSTAGE 2
-#define EPI_PITCH 68  // floats; epilogue staging row pitch (272 B)
-#define LDS_BYTES (4 * 64 * EPI_PITCH * 4)  // 69632 >= NSTAGE*STAGE_BYTES
+static_assert(LDS_BYTES >= NSTAGE * STAGE_BYTES, "kernel S: the epilogue staging covers the operand stages");
 
 __device__ __attribute__((aligned(16))) uint32_t g_ca_zero_page[4];
 __device__ int g_ca_epi_general = 0;  // tests: 1 = every wave tile takes the general epilogue walk (ca_gemm_debug_general_epilogue)
@@ -282,107 +279,11 @@ __device__ __forceinline__ void lds_wait(bf16x8_t (&f)[4]) {
   asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]));
 }
 
-// XCD-aware tile rasterisation.  Workgroups are dealt round-robin over the 8 XCDs (blocks b and
-// b+8 share an L2), and the tiles that are resident together on one XCD should share operand
-// panels: they stream the same K-slices at about the same time, so each slice is pulled across
-// the fabric once per XCD and served to the other tiles from that XCD's 4-MiB L2.  The grid is
-// cut into super-blocks of SBM x SBN tiles (= the number of tiles one XCD holds at once); the
-// i-th workgroup of XCD x works on tile (i % (SBM*SBN)) of super-block (i / (SBM*SBN))*8 + x.
-// Placement only affects speed: any dispatch order gives the same result.
-// Small / medium grids: the tile grid is cut into exactly 8 rectangular blocks, one per XCD (bm x bn blocks with
-// bm * bn = 8, the split that minimises block height + width = the operand bands an XCD has to stream).
-// xcd_split returns bm; the block is hb x wb tiles.
-__host__ __device__ __forceinline__ int xcd_split(int ntm, int ntn, int& hb, int& wb) {
-  int best = 1, cost = 1 << 30;
-#pragma unroll
-  for (int bm = 1; bm <= 8; bm *= 2) {
-    const int bn = 8 / bm;
-    const int c = (ntm + bm - 1) / bm + (ntn + bn - 1) / bn;
-    if (c < cost) {
-      cost = c;
-      best = bm;
-    }
-  }
-  hb = (ntm + best - 1) / best;
-  wb = (ntn + 8 / best - 1) / (8 / best);
-  return best;
-}
-// Tile `l` of a grid in run order: the shorter grid dimension runs fastest, so a run of consecutive tiles covers a
-// compact band of the grid.
-__device__ __forceinline__ void run_tile(int l, int ntm, int ntn, int& tm, int& tn) {
-  if (ntn <= ntm) {
-    tm = l / ntn;
-    tn = l % ntn;
-  } else {
-    tn = l / ntm;
-    tm = l % ntm;
-  }
-}
-// The rectangular split leaves XCDs unevenly loaded when the grid does not divide (5 x 5 tiles: 6, 6, 3, 0, 4, 4, 2,
-// 0 per XCD): where it would pad by more than a quarter, each XCD takes a run of ceil(T / 8) consecutive tiles.
-// bal (CaGemmDesc.xcd_balanced, set by the library beside a resident collective): always runs - every XCD gets
-// ceil(T / 8) tiles.  The rectangular split may hand one XCD exactly its 32 CUs' worth of a 240-tile grid (32, 32, ...,
-// 24, 24): with two CUs of an XCD held by another kernel that XCD runs a second round and the launch takes twice as long.
-__host__ __device__ __forceinline__ bool xcd_use_runs(int ntm, int ntn, int hb, int wb, bool bal = false) {
-  return bal || 8 * hb * wb * 4 > ntm * ntn * 5;
-}
-__host__ __device__ __forceinline__ int xcd_grid(int ntm, int ntn, bool bal = false) {
-  if (ntm * ntn <= 8) return ntm * ntn;  // a handful of tiles (batched attention-sized problems): plain numbering
-  int hb, wb;
-  xcd_split(ntm, ntn, hb, wb);
-  if (xcd_use_runs(ntm, ntn, hb, wb, bal)) return 8 * ((ntm * ntn + 7) / 8);
-  return 8 * hb * wb;
-}
-// tile of block `bid` under that split (false = padding block)
-__device__ __forceinline__ bool xcd_tile(int bid, int ntm, int ntn, int& tm, int& tn, bool bal = false) {
-  if (ntm * ntn <= 8) {
-    tm = bid / ntn;
-    tn = bid % ntn;
-    return true;
-  }
-  int hb, wb;
-  const int bm = xcd_split(ntm, ntn, hb, wb);
-  const int bn = 8 / bm;
-  const int x = bid & 7, idx = bid >> 3;
-  if (xcd_use_runs(ntm, ntn, hb, wb, bal)) {
-    const int l = x * ((ntm * ntn + 7) / 8) + idx;
-    run_tile(l, ntm, ntn, tm, tn);
-    return l < ntm * ntn;
-  }
-  const int bi = x / bn, bj = x % bn;
-  tm = bi * hb + idx / wb;
-  tn = bj * wb + idx % wb;
-  return tm < ntm && tn < ntn;
-}
-template <int SBM, int SBN>
-__device__ __forceinline__ bool tile_of_block_g(int bid, int grid, int ntm, int ntn, int& tm, int& tn, bool bal = false);
+// XCD-aware tile rasterisation: gemm_plan.h (shared with the host's grid arithmetic).  The tile of block `bid` of this
+// launch's own grid:
 template <int SBM, int SBN>
 __device__ __forceinline__ bool tile_of_block(int bid, int ntm, int ntn, int& tm, int& tn, bool bal = false) {
   return tile_of_block_g<SBM, SBN>(bid, (int)gridDim.x, ntm, ntn, tm, tn, bal);
-}
-// the same with the size of the (virtual) grid given: persistent workgroups walk a grid larger than the launch
-template <int SBM, int SBN>
-__device__ __forceinline__ bool tile_of_block_g(int bid, int grid, int ntm, int ntn, int& tm, int& tn, bool bal) {
-  if (grid == xcd_grid(ntm, ntn, bal)) {
-    // small problem (fewer than 4 super-blocks per XCD): one rectangular block of tiles per XCD, so an L2 only
-    // streams the operand bands of its block.  (Plain round-robin numbering gave each XCD one tile COLUMN: all of
-    // A streamed into every L2, 8x the bytes in the PMC counters.)
-    return xcd_tile(bid, ntm, ntn, tm, tn, bal);
-  }
-  const int x = bid & 7, i = bid >> 3;
-  const int per = SBM * SBN;
-  const int sb = (i / per) * 8 + x, t = i % per;
-  const int nsbn = (ntn + SBN - 1) / SBN;
-  const int sbm = sb / nsbn, sbn = sb % nsbn;
-  tm = sbm * SBM + (t % SBM);
-  tn = sbn * SBN + (t / SBM);
-  return tm < ntm && tn < ntn;
-}
-template <int SBM, int SBN>
-static inline unsigned tile_grid(int ntm, int ntn, bool bal = false) {
-  if (ntm * ntn < 4 * 8 * SBM * SBN) return (unsigned)xcd_grid(ntm, ntn, bal);  // fewer than 4 super-blocks per XCD
-  const int nsb = ((ntm + SBM - 1) / SBM) * ((ntn + SBN - 1) / SBN);
-  return (unsigned)(((nsb + 7) / 8) * 8 * SBM * SBN);
 }
 
 // ---- epilogue --------------------------------------------------------------------------------
@@ -435,53 +336,10 @@ __device__ __forceinline__ void ca_store_fp8x8(unsigned char* dst, const float (
 // predicates are gone, the flat element index of the dropout hash advances by a constant.  Same arithmetic in the same
 // order as the general walk: the results are bit-identical (tests/test_kernels_gpu.py compares ragged and interior tiles
 // of one launch against the same reference).
-// ---- slab staging (kernel X, round 5) ---------------------------------------------------------------------------
-// The classic staging parks a wave's whole 64 x 64 fp32 tile (17 KB, 139 KB for the 8 waves of kernel X: every byte of
-// the operand stages), so nothing of the next tile can be in flight while a tile leaves.  Slab staging parks 16 rows
-// at a time in a 4-KiB region per wave that lies BEHIND the two operand stages (128 KiB + 8 x 4 KiB = all 160 KiB of
-// LDS), walks them in the same two passes of 8 rows x 64 columns per lane group as before (same lane -> element
-// assignment, same order: bit-identical outputs and sums of squares) and lets kernel X request the next tile's first
-// K-step before the epilogue starts.  The 16 x 64 slab has no row padding: 16-byte chunk c of row r sits at chunk
-// c ^ r, which is conflict-free for the parked fragments (8 consecutive rows of one chunk column per ds_write_b128
-// group) and for the row-major reads (the hardware's 16-lane ds_read_b128 groups cover 16 different chunks).
-// Which 16 rows are parked is a run-time choice in a rolled loop - made by a wave-uniform switch over register
-// copies, because a run-time index into the accumulator array would send it through scratch memory.
-#define SLAB_BYTES 4096
-__device__ __forceinline__ void slab_park(const f32x4_t (&acc)[4][4], int i4, float* slab, int lane) {
-  const int r = lane & 15, g = lane >> 4;
-  float* row = slab + r * 64;
-  float* p0 = row + ((g ^ r) << 2);
-  float* p1 = row + (((4 + g) ^ r) << 2);
-  float* p2 = row + (((8 + g) ^ r) << 2);
-  float* p3 = row + (((12 + g) ^ r) << 2);
-  // the stores sit INSIDE the cases: straight from the accumulator registers, no copies (the asm statements keep the
-  // cases as branches: as selects they would cost 3 x 16 v_cndmask per slab)
-#define SLAB_CASE(I)                 \
-  asm volatile("; slab rows " #I);   \
-  *(f32x4_t*)p0 = acc[I][0];         \
-  *(f32x4_t*)p1 = acc[I][1];         \
-  *(f32x4_t*)p2 = acc[I][2];         \
-  *(f32x4_t*)p3 = acc[I][3];
-  switch (i4) {
-    case 0: SLAB_CASE(0) break;
-    case 1: SLAB_CASE(1) break;
-    case 2: SLAB_CASE(2) break;
-    default: SLAB_CASE(3) break;
-  }
-#undef SLAB_CASE
-}
-// the 8 consecutive columns 8 (lane & 7) .. of row p * 8 + (lane >> 3) of the parked slab
-__device__ __forceinline__ void slab_read(const float* slab, int p, int lane, f32x4_t& a4, f32x4_t& b4) {
-  const int r = p * 8 + (lane >> 3), c = 2 * (lane & 7);
-  const float* row = slab + r * 64;
-  a4 = *(const f32x4_t*)(row + ((c ^ r) << 2));
-  b4 = *(const f32x4_t*)(row + (((c + 1) ^ r) << 2));
-}
-
-template <int EPI, bool F32, bool DROP, bool SLAB = false>
+template <int EPI, bool F32, bool DROP>
 __device__ __forceinline__ void gemm_epilogue_fast(const CaGemmDesc& d, const float* wt, int lane, int mw, int nb, int z,
                                                    int64_t zoffC, int64_t zoffR, const float (&bias8)[8], float& ssq,
-                                                   float& amx, const f32x4_t (*acc)[4][4] = nullptr) {
+                                                   float& amx) {
   const int M = d.M, N = d.N;
   const float alpha = d.alpha;
   const float keep_scale = DROP ? 1.f / (1.f - d.dropout_p) : 1.f;
@@ -510,31 +368,12 @@ __device__ __forceinline__ void gemm_epilogue_fast(const CaGemmDesc& d, const fl
     dthr = ca_dropout_threshold(d.dropout_p);
   }
   const unsigned int dgstep = (unsigned int)(istep >> 2);
-  if (SLAB) slab_park(*acc, 0, const_cast<float*>(wt), lane);
-#pragma unroll 1
-  for (int i4 = 0; i4 < (SLAB ? 4 : 1); ++i4) {
-  // slab i4's 16 rows go to registers first, then the next 16 rows are parked (LDS operations of a wave execute in
-  // order: the reads see the old slab) - the stores complete under this slab's arithmetic
-  f32x4_t sa[2], sb[2];
-  if (SLAB) {
-    slab_read(wt, 0, lane, sa[0], sb[0]);
-    slab_read(wt, 1, lane, sa[1], sb[1]);
-    if (i4 < 3) slab_park(*acc, i4 + 1, const_cast<float*>(wt), lane);
-  }
 #pragma unroll 2
-  for (int itl = 0; itl < (SLAB ? 2 : 8); ++itl) {
-    const int it = SLAB ? 2 * i4 + itl : itl;
+  for (int it = 0; it < 8; ++it) {
     const u16x8_t r_cur = r_next;
     if (NEEDS_R && it < 7) r_next = *(const u16x8_t*)(Rp + (it + 1) * rstep);
-    f32x4_t a4, b4;
-    if (SLAB) {
-      a4 = sa[itl];
-      b4 = sb[itl];
-    } else {
-      const float* wr = wt + (it * 8 + r0) * EPI_PITCH + c0;
-      a4 = *(const f32x4_t*)wr;
-      b4 = *(const f32x4_t*)(wr + 4);
-    }
+    const float* wr = wt + (it * 8 + r0) * EPI_PITCH + c0;
+    const f32x4_t a4 = *(const f32x4_t*)wr, b4 = *(const f32x4_t*)(wr + 4);
     float v[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = (e < 4 ? a4[e] : b4[e - 4]) * alpha + bias8[e];
@@ -605,12 +444,10 @@ __device__ __forceinline__ void gemm_epilogue_fast(const CaGemmDesc& d, const fl
     }
     coff += cstep;
   }
-  }  // slabs
 }
 
 // PARKED: the 64 x 64 staging tile `wave` already holds the accumulators (kernel M: two waves fill one tile)
-// SLAB: `smem` is the wave's own 4-KiB slab (see slab_park); the 64 x 64 tile goes through it 16 rows at a time
-template <bool PARKED = false, bool SLAB = false>
+template <bool PARKED = false>
 __device__ __forceinline__ void gemm_epilogue(const CaGemmDesc& d, f32x4_t (&acc)[4][4], char* smem,
                                               int wave, int lane, int mw, int nw, int z, int z1,
                                               int z2, const float (*bias_pre)[8] = nullptr) {
@@ -645,8 +482,8 @@ __device__ __forceinline__ void gemm_epilogue(const CaGemmDesc& d, f32x4_t (&acc
   u16x8_t r_next = {0, 0, 0, 0, 0, 0, 0, 0};
   load_r(0, r_next);
 
-  float* wt = SLAB ? (float*)smem : (float*)smem + wave * (64 * EPI_PITCH);
-  if (!PARKED && !SLAB) {
+  float* wt = (float*)smem + wave * (64 * EPI_PITCH);
+  if (!PARKED) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -655,8 +492,7 @@ __device__ __forceinline__ void gemm_epilogue(const CaGemmDesc& d, f32x4_t (&acc
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-private region: no barrier
   }
   const bool c8_on = d.C8 != nullptr && (epi == CA_EPI_GELU || epi == CA_EPI_DGELU);
-  // (slab staging: every lane keeps parking its share of the rows inside the walk, also one without valid columns)
-  if (!SLAB && nvalid <= 0 && d.c_sumsq == nullptr && !c8_on) return;
+  if (nvalid <= 0 && d.c_sumsq == nullptr && !c8_on) return;
   float ssq = 0.f;  // sum of squares of the fp32 values this lane stores (c_sumsq)
   float amx = 0.f;  // max |gelu| this lane stores (C8)
   const float s8 = c8_on ? d.c8_scale[0] : 1.f;
@@ -668,7 +504,7 @@ __device__ __forceinline__ void gemm_epilogue(const CaGemmDesc& d, f32x4_t (&acc
                         (d.out_f32 || !d.accumulate) && (!has_gelu || (epi == CA_EPI_GELU && d.C2 != nullptr && !d.out_f32)) &&
                         !(d.out_f32 && epi != CA_EPI_NONE) && !(drop_on && epi == CA_EPI_NONE);
   if (interior) {
-#define EPI_FAST(E, F, D) gemm_epilogue_fast<E, F, D, SLAB>(d, wt, lane, mw, nb, z, zoffC, zoffR, bias8, ssq, amx, &acc)
+#define EPI_FAST(E, F, D) gemm_epilogue_fast<E, F, D>(d, wt, lane, mw, nb, z, zoffC, zoffR, bias8, ssq, amx)
     if (d.out_f32) {
       EPI_FAST(CA_EPI_NONE, true, false);
     } else if (epi == CA_EPI_NONE) {
@@ -684,19 +520,13 @@ __device__ __forceinline__ void gemm_epilogue(const CaGemmDesc& d, f32x4_t (&acc
   } else {
 #pragma unroll 1
   for (int it = 0; it < 8; ++it) {
-    if (SLAB && (it & 1) == 0) slab_park(acc, it >> 1, wt, lane);  // (before any `continue`: every lane parks its rows)
     const int ml = it * 8 + (lane >> 3);
     const int m = mw + ml;
     const u16x8_t r_cur = r_next;
     load_r(it + 1, r_next);
     if (m >= M || nvalid <= 0) continue;
-    f32x4_t a4, b4;
-    if (SLAB) {
-      slab_read(wt, it & 1, lane, a4, b4);
-    } else {
-      a4 = *(const f32x4_t*)(wt + ml * EPI_PITCH + 8 * (lane & 7));
-      b4 = *(const f32x4_t*)(wt + ml * EPI_PITCH + 8 * (lane & 7) + 4);
-    }
+    const f32x4_t a4 = *(const f32x4_t*)(wt + ml * EPI_PITCH + 8 * (lane & 7));
+    const f32x4_t b4 = *(const f32x4_t*)(wt + ml * EPI_PITCH + 8 * (lane & 7) + 4);
     float v[8], v2[8], r[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -1005,7 +835,7 @@ __global__ __launch_bounds__(256) void ca_gemm_kernel(const CaGemmDesc d) {
 // ahead, counted vmcnt: 4 pieces per wave and tile).  Epilogue: the two waves of a 64x64 quadrant park their halves in
 // one staging tile, the even one walks it through the shared epilogue.
 #define M_NST 4
-#define M_LDS_BYTES (2 * M_NST * TILE_BYTES)  // 131072 >= 4 quadrants * 64*68*4 (69632) of epilogue staging
+static_assert(M_LDS_BYTES == 2 * M_NST * TILE_BYTES, "131072 >= 4 quadrants * 64*68*4 (69632) of epilogue staging");
 template <int N>
 __device__ __forceinline__ void lds_wait_n(bf16x8_t (&f)[N]) {
   if constexpr (N == 4)
@@ -1137,21 +967,9 @@ __global__ __launch_bounds__(512) void ca_gemm_kernel_m(const CaGemmDesc d) {
 // ---- kernel X: 256x256 tile, 8 waves (2x4, 128x64 each), 2 LDS stages, one workgroup per CU ----------
 // Half the LDS-fill bytes per FLOP of kernel S (the fill stream is what bounds S);
 // used when both output dimensions are large enough to give every CU a tile.
-#define XBM 256
-#define XBN 256
 #define XTILE (XBM * BK * 2)  // 32 KiB per operand tile
 #define XSTAGE (2 * XTILE)
-#define X_LDS_BYTES (8 * 64 * EPI_PITCH * 4)  // 139264 >= 2 stages * 64 KiB (classic staging: the fp8 256x256 kernel)
-#define X_SLAB_BASE (2 * XSTAGE)             // bf16 kernel X: 8 epilogue slabs of 4 KiB behind the two stages
-#define X_SLAB_LDS (X_SLAB_BASE + 8 * SLAB_BYTES)  // 163840 = all 160 KiB of a CU's LDS
-#ifndef CA_X_SLAB
-// 1: slab staging + the next tile's first K-step requested under the epilogue.  Built and measured in round 5 (same box,
-// interleaved, profiles/r05_gemm_shapes.txt): 3 % SLOWER on the plain FFN launch and equal on the GELU launches in its
-// first form, 20 % slower with the slab's reads hoisted above the next park - the epilogue of a 256 x 256 tile is bound
-// by the 128-256 KB every CU stores at the same moment (12.5 B/clk per CU = the chip's HBM write rate), not by its LDS
-// staging or by the prologue the early request hides.  The default stays the classic staging; -DCA_X_SLAB=1 builds it.
-#define CA_X_SLAB 0
-#endif
+static_assert(X_LDS_BYTES >= 2 * XSTAGE, "kernel X: the epilogue staging covers the two operand stages");
 
 // grp.count > 1: a grouped launch of up to X_GROUP_MAX independent problems of the same operand form
 // (ca_gemm_bf16_group): block ranges map to problems, each with plain row-major tile numbering.
@@ -1199,24 +1017,17 @@ __device__ __forceinline__ void gemm_x_body(const CaGemmGroup& grp) {
   const int npx = ((int)gridDim.x - xcd + 7) >> 3;  // workgroups of this XCD in the launch
   const int nvx = (vgrid - xcd + 7) >> 3;           // virtual blocks of this XCD
   const int ndyn = nvx > npx ? nvx - npx : 0;       // ... handed out dynamically
-  // LDS: A0 | A1 | B0 | B1 (the two operand stages, 128 KiB), then one 4-KiB epilogue slab per wave (slab_park).
-  // The word pair that carries the next block's index sits at the head of wave 0's slab: thread 0 writes it at the
-  // start of a tile (its own wave's previous epilogue is over by program order), every wave reads it behind the main
-  // loop - at least one K-step barrier after the write - and in FRONT of the barrier that ends the tile's LDS reads;
-  // only behind that barrier does wave 0's epilogue overwrite it.
-  constexpr bool XSLAB = CA_X_SLAB != 0;
-  volatile unsigned* nextw = (volatile unsigned*)(smem + (XSLAB ? X_SLAB_BASE : X_LDS_BYTES));  // two words, alternating per iteration
-  char* const slab = smem + X_SLAB_BASE + wave * SLAB_BYTES;
-  // Loader state lives outside the tile loop: with one problem per launch (the same descriptor for every tile) the
-  // NEXT tile's loaders are set up and its first K-step is requested behind the barrier that ends this tile's LDS
-  // reads, i.e. under this tile's epilogue (`pre`) - the operand stages are free by then, the epilogue only touches
-  // the slabs.  K-major operands and plain MN-major ones stream through a scalar base (KMajorStream / MNMajorStream);
-  // MN-major operands with segmented rows (KS) keep the per-lane pointer walk.
+  // LDS: A0 | A1 | B0 | B1 (the two operand stages, 128 KiB) in the first X_LDS_BYTES, which the epilogue reuses as
+  // eight 64 x 64 fp32 staging tiles, one per wave; behind them (X_LAUNCH_LDS = X_LDS_BYTES + 64) the word pair that
+  // carries a persistent workgroup's next block index.  Thread 0 writes a word at the start of a tile, every wave
+  // reads it behind the main loop - at least one K-step barrier after the write; the two words alternate per
+  // iteration, so the write of iteration i + 1 cannot overtake a read of iteration i.
+  volatile unsigned* nextw = (volatile unsigned*)(smem + X_LDS_BYTES);
+  // K-major operands and plain MN-major ones stream through a scalar base (KMajorStream / MNMajorStream); MN-major
+  // operands with segmented rows (KS) keep the per-lane pointer walk.
   KMajorStream<4> la_k, lb_k;
   MNMajorStream<4, 32> la_f, lb_f;
   MNMajorLoader<4, 32, KS> la_m, lb_m;
-  bool pre = false;
-  int pre_tm = 0, pre_tn = 0;
   int vb = (int)blockIdx.x;
   int dbase = npx, dcount = ndyn;  // dynamic blocks of this XCD: local indices dbase .. dbase + dcount - 1
   if (grp.cnt != nullptr && grp.dyn_first) {
@@ -1241,7 +1052,7 @@ __device__ __forceinline__ void gemm_x_body(const CaGemmGroup& grp) {
   }
   bool live = true;
   int which = 0, gt = 0;
-  if (!pre && grp.count > 1) {
+  if (grp.count > 1) {
     // grouped launch: the group's tiles form one list (problem after problem, each in run order) and XCD x
     // (= block & 7) takes the x-th run of ceil(total / 8) of them: every XCD gets the same number of tiles
     // whatever the shapes, and a run covers a compact band of one or two problems.
@@ -1254,8 +1065,8 @@ __device__ __forceinline__ void gemm_x_body(const CaGemmGroup& grp) {
     }
   }
   const CaGemmDesc d = grp.d[which];
-  int tm = pre_tm, tn = pre_tn;
-  if (live && !pre) {
+  int tm = 0, tn = 0;
+  if (live) {
     if (grp.count > 1)
       run_tile(gt - grp.first[which], (d.M + XBM - 1) / XBM, (d.N + XBN - 1) / XBN, tm, tn);
     else
@@ -1282,7 +1093,7 @@ __device__ __forceinline__ void gemm_x_body(const CaGemmGroup& grp) {
     else
       lb_f.init(B, d.ldb, col0, d.N, wave, lane);
   };
-  if (!pre) init_loaders(m0, n0);
+  init_loaders(m0, n0);
 
   f32x4_t acc[8][4];
 #pragma unroll
@@ -1545,7 +1356,7 @@ __device__ __forceinline__ void gemm_x_body(const CaGemmGroup& grp) {
 #ifdef X_STAMPS
   const long long stamp_t0 = __builtin_amdgcn_s_memtime();
 #endif
-  if (!pre) burst(0);  // (else: requested under the previous tile's epilogue)
+  burst(0);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   zero_tail(0);
   __builtin_amdgcn_s_barrier();
@@ -1581,31 +1392,14 @@ __device__ __forceinline__ void gemm_x_body(const CaGemmGroup& grp) {
       if (lane < 16 && m < d.M) d.a_colsum[(int64_t)tn * d.a_colsum_ld + m] = s;  // this tile column's share
     }
   }
-  // this workgroup's next block (thread 0 wrote the word at the start of the tile, K-step barriers ago; it is read in
-  // front of the barrier below, behind which wave 0's epilogue may overwrite it)
+  // this workgroup's next block (thread 0 wrote the word at the start of the tile, K-step barriers ago)
   unsigned nxt = 0;
   if (grp.cnt != nullptr) nxt = (unsigned)__builtin_amdgcn_readfirstlane((int)nextw[iter & 1]);  // wave-uniform by construction
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();  // every wave has read the last K-step: the operand stages are free
   asm volatile("" ::: "memory");
-  pre = false;
-  if (grp.cnt != nullptr) {
-    vb_next = nxt < (unsigned)dcount ? xcd + 8 * (dbase + (int)nxt) : vgrid;
-    if constexpr (!KS && XSLAB) {
-      if (grp.count <= 1 && vb_next < vgrid) {
-        // one problem per launch: the next tile's first K-step goes out now and lands under this tile's epilogue
-        int tmn = 0, tnn = 0;
-        if (tile_of_block_g<4, 8>(vb_next, vgrid, (d.M + XBM - 1) / XBM, (d.N + XBN - 1) / XBN, tmn, tnn, d.xcd_balanced != 0)) {
-          init_loaders(tmn * XBM, tnn * XBN);
-          burst(0);
-          pre = true;
-          pre_tm = tmn;
-          pre_tn = tnn;
-        }
-      }
-    }
-  }
-  // two 64-row halves through the shared epilogue, 16 rows at a time through the wave's slab
+  if (grp.cnt != nullptr) vb_next = nxt < (unsigned)dcount ? xcd + 8 * (dbase + (int)nxt) : vgrid;
+  // two 64-row halves through the shared epilogue
 #pragma unroll
   for (int ih = 0; ih < 2; ++ih) {
     f32x4_t half[4][4];
@@ -1613,16 +1407,10 @@ __device__ __forceinline__ void gemm_x_body(const CaGemmGroup& grp) {
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) half[i][j] = acc[ih * 4 + i][j];
-    if constexpr (XSLAB) {
-      gemm_epilogue<false, true>(d, half, slab, wave, lane, m0 + wm * 128 + ih * 64, n0 + wn * 64, z, z1, z2, KS ? nullptr : &xbias);
-    } else {
-      gemm_epilogue(d, half, smem, wave, lane, m0 + wm * 128 + ih * 64, n0 + wn * 64, z, z1, z2, KS ? nullptr : &xbias);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // staging reads done before it is overwritten
-    }
+    gemm_epilogue(d, half, smem, wave, lane, m0 + wm * 128 + ih * 64, n0 + wn * 64, z, z1, z2, KS ? nullptr : &xbias);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // staging reads done before it is overwritten
   }
-  if constexpr (!XSLAB) {
-    if (grp.cnt != nullptr) __syncthreads();  // every wave is done with the staging area before the next tile lands in it
-  }
+  if (grp.cnt != nullptr) __syncthreads();  // every wave is done with the staging area before the next tile lands in it
 #ifdef X_STAMPS
   {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1642,7 +1430,6 @@ __device__ __forceinline__ void gemm_x_body(const CaGemmGroup& grp) {
   }  // live
   else if (grp.cnt != nullptr) {
     // a padding block of the virtual grid: no K-step barrier separates thread 0's write from the reads
-    pre = false;
     __syncthreads();
     const unsigned i = (unsigned)__builtin_amdgcn_readfirstlane((int)nextw[iter & 1]);
     vb_next = i < (unsigned)dcount ? xcd + 8 * (dbase + (int)i) : vgrid;
@@ -1679,12 +1466,10 @@ void ca_gemm_kernel_x<CA_KMAJOR, CA_KMAJOR, false>(const CaGemmGroup grp) {
 // barrier, waves 4-7 one block later).  A K-step has two blocks of 16 MFMAs (k-half 0, k-half 1) per wave.  The 48-KiB
 // stages leave room for a ring of three: the LDS-DMA runs TWO tiles ahead behind a counted vmcnt (6 pieces per wave and
 // tile), which is what keeps the loop fed when the optimiser's traffic beside the forward stretches the fetch latency.
-#define LBM 256
-#define LBN 128
 #define LA_BYTES (LBM * BK * 2)  // 32 KiB
 #define LB_BYTES (LBN * BK * 2)  // 16 KiB
 #define L_NST 3
-#define L_LDS_BYTES (L_NST * (LA_BYTES + LB_BYTES))  // 147456 >= 8 waves * 64*68*4 (139264) epilogue staging
+static_assert(L_LDS_BYTES == L_NST * (LA_BYTES + LB_BYTES), "147456 >= 8 waves * 64*68*4 (139264) epilogue staging");
 
 template <int AL, int BL>
 __global__ __launch_bounds__(512) void ca_gemm_kernel_l(const CaGemmDesc d) {
@@ -1914,7 +1699,6 @@ __global__ __launch_bounds__(512) void ca_gemm_kernel_l(const CaGemmDesc d) {
 // memory round trip) disappears from the per-token chain; bit-identical to the two launches.  The first eight weight
 // fragments of every wave (all of them at K = 1024) are asked for BEFORE the prologue, so the statistics run under
 // the weight fetch.
-#define SKINNY_LN_PAD 32  // bf16 elements between LDS rows beyond K: 64 B, lanes r and r + 1 then sit 16 banks apart
 // NCH: 64-lane rounds of 8-element chunks a row takes (K <= 512 NCH), 0 = no LayerNorm prologue
 // Round 5: 33 .. 128 rows (an evaluation run decodes more clips per step than 32 - R/config/evaluation.yaml:20,
 // R/src/coral/evaluate.py:56-60) run the SAME 32-row kernel on a two-dimensional grid: blockIdx.y picks the block of 32
@@ -2220,16 +2004,32 @@ static unsigned x_device_cus() {
   }();
   return ncu;
 }
-static unsigned x_compute_cus() {
-  const unsigned ncu = x_device_cus();
-  if (g_compute_cus <= 0) return ncu;
-  const unsigned c = (unsigned)(g_compute_cus >= 8 ? (g_compute_cus / 8) * 8 : 8);
-  return c < ncu ? c : ncu;
-}
-static int g_force_kernel = 0;  // 0 auto, 1 force 128x128, 2 force 256x128 (tests / tuning)
+static int g_force_kernel = 0;  // 0 auto, 1 force 128x128, 2 force 256x128, 3 force 256x256, 5 force kernel M (tests / tuning)
 extern "C" int ca_gemm_force_kernel(int which) {
   g_force_kernel = which;
   return CA_OK;
+}
+// The tuning values of the kernel-choice rule (gemm_plan.h): the environment, read once, and the process's settings.
+static GemmKnobs gemm_knobs() {
+  static const GemmKnobs env = [] {
+    GemmKnobs k;
+    const auto read = [](const char* name, int& v) { if (const char* e = getenv(name)) v = atoi(e); };
+    read("CA_X_PERSIST", k.x_persist);
+    read("CA_SKINNY_MB1", k.skinny_mb1);
+    read("CA_SKINNY_MB1_ROWS", k.skinny_mb1_rows);
+    read("CA_SKINNY_NT", k.skinny_nt);
+    read("CA_SKINNY_U", k.skinny_u);
+    read("CA_GEMM_PREFER_L", k.prefer_l);
+    read("CA_GEMM_L_OVER_X", k.l_over_x);
+    read("CA_GEMM_L_MIN", k.l_min);
+    read("CA_GEMM_M", k.m_max);
+    return k;
+  }();
+  GemmKnobs k = env;
+  k.force_kernel = g_force_kernel;
+  k.compute_cus = g_compute_cus;
+  k.device_cus = x_device_cus();
+  return k;
 }
 static int ca_gemm_launch(const CaGemmDesc* desc, void* stream);
 static int g_last_kind = 0;  // kernel chosen by the last launch: 0 = S, 1 = L, 2 = X
@@ -2540,9 +2340,102 @@ __global__ __launch_bounds__(512) void ca_gemm_fp8_kernel_x(const CaGemmDesc d) 
   }
 }
 
-extern "C" int ca_gemm_fp8(const CaGemmDesc* desc, void* stream) {
-  CA_CHECK_ARG(desc != nullptr, "ca_gemm_fp8: null descriptor");
-  const CaGemmDesc& d = *desc;
+// ---- host dispatch: validate, plan (gemm_plan.h), launch -------------------------------------------------------------
+// The kernel instantiations a plan can name, per family; layouts indexed a_layout * 2 + b_layout (+ 4 with segmented K).
+typedef void (*DescKernel)(const CaGemmDesc);
+typedef void (*GroupKernel)(const CaGemmGroup);
+#define LAY4(K) K<0, 0>, K<0, 1>, K<1, 0>, K<1, 1>
+#define LAY4_KS(K, KS) K<0, 0, KS>, K<0, 1, KS>, K<1, 0, KS>, K<1, 1, KS>
+static const DescKernel k_gemm_s[8] = {LAY4_KS(ca_gemm_kernel, false), LAY4_KS(ca_gemm_kernel, true)};
+static const DescKernel k_gemm_m[4] = {LAY4(ca_gemm_kernel_m)};
+static const DescKernel k_gemm_l[4] = {LAY4(ca_gemm_kernel_l)};
+static const GroupKernel k_gemm_x[8] = {LAY4_KS(ca_gemm_kernel_x, false), LAY4_KS(ca_gemm_kernel_x, true)};
+static const DescKernel k_gemm_fp8[2] = {ca_gemm_fp8_kernel, ca_gemm_fp8_kernel_x};  // 128 x 128, 256 x 256
+#undef LAY4_KS
+#undef LAY4
+struct SkinnyKernel {
+  int mb, nch, u, nt;
+  DescKernel fn;
+};
+#define SK(MB, NCH, U, NT) {MB, NCH, U, NT, ca_gemm_skinny_kernel<MB, NCH, U, NT>}
+#define SK_NT(MB, NCH, U) SK(MB, NCH, U, 16), SK(MB, NCH, U, 8), SK(MB, NCH, U, 4)
+static const SkinnyKernel k_gemm_skinny[] = {
+    SK_NT(1, 0, 8), SK_NT(1, 0, 16), SK_NT(1, 0, 32), SK(2, 0, 8, 16),                                  // plain
+    SK_NT(1, 2, 8), SK_NT(1, 3, 8),  SK_NT(1, 4, 8),  SK(2, 2, 8, 16), SK(2, 3, 8, 16), SK(2, 4, 8, 16)  // LayerNorm(A)
+};
+#undef SK_NT
+#undef SK
+
+// dynamic LDS beyond the default limit is allowed per kernel: once per process for each family
+enum { LDS_FAM_M, LDS_FAM_L, LDS_FAM_X, LDS_FAM_SKINNY_LN, LDS_FAM_FP8_S, LDS_FAM_FP8_X, LDS_FAM_COUNT };
+static bool g_lds_allowed[LDS_FAM_COUNT];
+template <typename K>
+static void allow_lds(int fam, const K* kernels, int n, size_t bytes) {
+  if (g_lds_allowed[fam]) return;
+  for (int i = 0; i < n; ++i) hipFuncSetAttribute((const void*)kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  g_lds_allowed[fam] = true;
+}
+
+static int gemm_launch_skinny(const GemmPlan& p, const CaGemmDesc& d, hipStream_t s) {
+  if (p.nch > 0 && !g_lds_allowed[LDS_FAM_SKINNY_LN]) {
+    for (const SkinnyKernel& k : k_gemm_skinny)
+      if (k.nch > 0) hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    g_lds_allowed[LDS_FAM_SKINNY_LN] = true;
+  }
+  for (const SkinnyKernel& k : k_gemm_skinny)
+    if (k.mb == p.mb && k.nch == p.nch && k.u == p.u && k.nt == p.nt) {
+      CA_LAUNCH(k.fn, dim3(p.grid_x, p.grid_y), dim3(p.block), p.lds, s, d);
+      return CA_OK;
+    }
+  ca_set_error("ca_gemm_bf16: no skinny kernel <%d, %d, %d, %d>", p.mb, p.nch, p.u, p.nt);
+  return CA_ERR_UNSUPPORTED;
+}
+// kernel X, bf16: a persistent launch takes one of the counter slots (launches that may be in flight together use
+// different ones); without the counters it falls back to one workgroup per tile
+static void gemm_launch_x(const GemmPlan& p, CaGemmGroup& g, hipStream_t s) {
+  static unsigned seq = 0;
+  allow_lds(LDS_FAM_X, k_gemm_x, 8, p.lds);
+  g.vgrid = (int)p.vgrid;
+  g.cnt = nullptr;
+  g.dyn_first = p.dyn_first;
+  dim3 grid(p.vgrid, 1, p.grid_z);
+  if (p.persistent) {
+    unsigned* base = nullptr;
+    if (hipGetSymbolAddress((void**)&base, HIP_SYMBOL(g_x_cnt)) == hipSuccess && base) {
+      g.cnt = base + (size_t)(seq++ % X_CNT_SLOTS) * 8;
+      grid.x = p.grid_x;
+    }
+  }
+  CA_LAUNCH(k_gemm_x[p.lay + 4 * p.ks], grid, dim3(p.block), p.lds, s, g);
+}
+// Launches the kernel instantiation the plan names.  grp: the problem list of a grouped launch (kernel X), else null.
+static int gemm_launch_plan(const GemmPlan& p, const CaGemmDesc& d, CaGemmGroup* grp, hipStream_t s, const char* who) {
+  const dim3 grid(p.grid_x, p.grid_y, p.grid_z), block(p.block);
+  if (p.fp8) {
+    const int x = p.family == GEMM_X ? 1 : 0;
+    allow_lds(x ? LDS_FAM_FP8_X : LDS_FAM_FP8_S, &k_gemm_fp8[x], 1, p.lds);
+    CA_LAUNCH(k_gemm_fp8[x], grid, block, p.lds, s, d);
+  } else if (p.family == GEMM_SKINNY) {
+    const int rc = gemm_launch_skinny(p, d, s);
+    if (rc != CA_OK) return rc;
+  } else if (p.family == GEMM_X) {
+    CaGemmGroup one;  // a plain launch is a group of one: problem 0, no tile list
+    if (!grp) one.d[0] = d, one.count = 0, one.first[0] = 0, one.total = 0;
+    gemm_launch_x(p, grp ? *grp : one, s);
+  } else if (p.family == GEMM_L) {
+    allow_lds(LDS_FAM_L, k_gemm_l, 4, p.lds);
+    CA_LAUNCH(k_gemm_l[p.lay], grid, block, p.lds, s, d);
+  } else if (p.family == GEMM_M) {
+    allow_lds(LDS_FAM_M, k_gemm_m, 4, p.lds);
+    CA_LAUNCH(k_gemm_m[p.lay], grid, block, p.lds, s, d);
+  } else {
+    CA_LAUNCH(k_gemm_s[p.lay + 4 * p.ks], grid, block, p.lds, s, d);
+  }
+  CA_CHECK_LAUNCH(who);
+  return CA_OK;
+}
+
+static int gemm_validate_fp8(const CaGemmDesc& d) {
   CA_CHECK_ARG(d.A && d.B && (d.C || d.C2) && d.M > 0 && d.N > 0 && d.K > 0, "ca_gemm_fp8: bad argument");
   CA_CHECK_ARG(d.C8 == nullptr || ((d.epilogue == CA_EPI_GELU || d.epilogue == CA_EPI_DGELU) && d.c8_scale != nullptr && (d.ldc % 8) == 0 &&
                                    ((uintptr_t)d.C8 % 8) == 0),
@@ -2553,62 +2446,21 @@ extern "C" int ca_gemm_fp8(const CaGemmDesc* desc, void* stream) {
   CA_CHECK_ARG((d.K % 16) == 0 && (d.lda % 16) == 0 && (d.ldb % 16) == 0 && ((uintptr_t)d.A % 16) == 0 &&
                    ((uintptr_t)d.B % 16) == 0,
                "ca_gemm_fp8: K, lda, ldb must be multiples of 16 bytes and the operands 16-byte aligned");
-  static bool attr = false;
-  if (!attr) {
-    hipFuncSetAttribute((const void*)ca_gemm_fp8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    attr = true;
-  }
-  // the 256 x 256 kernel where it fills the chip (the bf16 rule), else the 128 x 128 one; ca_gemm_force_kernel(1 / 3)
-  // pins either for tests
-  const int xtm = (d.M + XBM - 1) / XBM, xtn = (d.N + XBN - 1) / XBN;
-  const int64_t xt = (int64_t)xtm * xtn;
-  const double xeff = ((double)xt / 256.0) / (double)((xt + 255) / 256);
-  const double xfill = ((double)d.M * d.N) / ((double)xtm * XBM * (double)xtn * XBN);
-  const bool use_x = g_force_kernel == 3 || (g_force_kernel == 0 && d.K >= 512 && xt >= 160 && xeff * xfill >= 0.70);
-  if (use_x) {
-    static bool attr_x = false;
-    if (!attr_x) {
-      hipFuncSetAttribute((const void*)ca_gemm_fp8_kernel_x, hipFuncAttributeMaxDynamicSharedMemorySize, X_LDS_BYTES);
-      attr_x = true;
-    }
-    hipLaunchKernelGGL(ca_gemm_fp8_kernel_x, dim3(tile_grid<4, 8>(xtm, xtn)), dim3(512), X_LDS_BYTES, (hipStream_t)stream, d);
-    CA_CHECK_LAUNCH("ca_gemm_fp8");
-    return CA_OK;
-  }
-  const int ntm = (d.M + BM - 1) / BM, ntn = (d.N + BN - 1) / BN;
-  hipLaunchKernelGGL(ca_gemm_fp8_kernel, dim3(tile_grid<8, 8>(ntm, ntn)), dim3(256), LDS_BYTES, (hipStream_t)stream, d);
-  CA_CHECK_LAUNCH("ca_gemm_fp8");
   return CA_OK;
 }
+extern "C" int ca_gemm_fp8(const CaGemmDesc* desc, void* stream) {
+  CA_CHECK_ARG(desc != nullptr, "ca_gemm_fp8: null descriptor");
+  const int rc = gemm_validate_fp8(*desc);
+  if (rc != CA_OK) return rc;
+  return gemm_launch_plan(gemm_plan_fp8(*desc, gemm_knobs()), *desc, nullptr, (hipStream_t)stream, "ca_gemm_fp8");
+}
 
-// Up to four independent GEMMs of the same operand form in one launch of kernel X (grouped launch): used where
+// Up to eight independent GEMMs of the same operand form in one launch of kernel X (grouped launch): used where
 // the problems do not fill the chip one by one (the four weight gradients of a transformer layer: 240 + 240 +
 // 184 + 64 tiles on 256 CUs at XLS-R-2B, 64 + 64 + 48 + 16 at d = 1024).  All must be un-batched, un-segmented
 // and plain (no epilogue, no bias).
-// Launch geometry of kernel X.  Default: persistent workgroups (one per CU) with dynamic tile pulls whenever the tile
-// grid is larger than the chip and un-batched; CA_X_PERSIST=0 restores one workgroup per tile.
-#define X_LAUNCH_LDS (CA_X_SLAB ? X_SLAB_LDS : X_LDS_BYTES + 64)
-static void x_launch_geometry(CaGemmGroup& g, unsigned vgrid, unsigned nbz, dim3& grid) {
-  static const int persist = [] { const char* e = getenv("CA_X_PERSIST"); return e ? atoi(e) : 1; }();
-  const unsigned ncu = x_compute_cus();
-  static unsigned seq = 0;
-  g.vgrid = (int)vgrid;
-  g.cnt = nullptr;
-  g.dyn_first = g_compute_cus > 0 ? 1 : 0;
-  grid = dim3(vgrid, 1, nbz);
-  if (persist && nbz == 1 && vgrid > ncu) {
-    unsigned* base = nullptr;
-    if (hipGetSymbolAddress((void**)&base, HIP_SYMBOL(g_x_cnt)) == hipSuccess && base) {
-      g.cnt = base + (size_t)(seq++ % X_CNT_SLOTS) * 8;
-      grid.x = ncu;
-    }
-  }
-}
-
-extern "C" int ca_gemm_bf16_group(const CaGemmDesc* descs, int32_t count, void* stream) {
+static int gemm_validate_group(const CaGemmDesc* descs, int32_t count) {
   CA_CHECK_ARG(descs && count >= 1 && count <= X_GROUP_MAX, "ca_gemm_bf16_group: 1..8 problems");
-  CaGemmGroup g;
-  int total = 0;
   for (int i = 0; i < count; ++i) {
     const CaGemmDesc* p = descs + i;
     CA_CHECK_ARG(p->A && p->B && p->C && p->M > 0 && p->N > 0 && p->K >= 64, "ca_gemm_bf16_group: bad problem %d", i);
@@ -2620,61 +2472,41 @@ extern "C" int ca_gemm_bf16_group(const CaGemmDesc* descs, int32_t count, void* 
     CA_CHECK_ARG(p->a_layout == descs->a_layout && p->b_layout == descs->b_layout,
                  "ca_gemm_bf16_group: the problems differ in operand form");
     CA_CHECK_ARG(p->c_sumsq == nullptr || p->epilogue == CA_EPI_NONE, "ca_gemm_bf16_group: c_sumsq needs a plain epilogue");
-    g.d[i] = *p;
+  }
+  return CA_OK;
+}
+extern "C" int ca_gemm_bf16_group(const CaGemmDesc* descs, int32_t count, void* stream) {
+  const int rc = gemm_validate_group(descs, count);
+  if (rc != CA_OK) return rc;
+  CaGemmGroup g;
+  int total = 0;
+  for (int i = 0; i < X_GROUP_MAX; ++i) {  // (the unused slots repeat problem 0 and own no tiles)
+    g.d[i] = descs[i < count ? i : 0];
     g.first[i] = total;
-    total += ((p->M + XBM - 1) / XBM) * ((p->N + XBN - 1) / XBN);
+    if (i < count) total += gemm_x_tiles(descs[i]);
   }
   g.total = total;
-  for (int i = count; i < X_GROUP_MAX; ++i) {
-    g.d[i] = descs[0];
-    g.first[i] = total;
-  }
   g.count = count > 1 ? count : 0;
-  static bool attr = false;
-#define XK(x, y) ca_gemm_kernel_x<x, y, false>
-  if (!attr) {
-    const void* fs[4] = {(const void*)XK(0, 0), (const void*)XK(0, 1), (const void*)XK(1, 0), (const void*)XK(1, 1)};
-    for (int i = 0; i < 4; ++i) hipFuncSetAttribute(fs[i], hipFuncAttributeMaxDynamicSharedMemorySize, X_LAUNCH_LDS);
-    attr = true;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  dim3 grid, block(512);
-  x_launch_geometry(g, (unsigned)(count > 1 ? 8 * ((total + 7) / 8)
-                                            : tile_grid<4, 8>((descs->M + XBM - 1) / XBM, (descs->N + XBN - 1) / XBN)), 1, grid);
-  const int lay = (descs->a_layout ? 2 : 0) + (descs->b_layout ? 1 : 0);
+  const GemmPlan p = gemm_plan_group(descs, count, gemm_knobs());
   ProfRec r;
   if (g_prof_on) {  // live roofline timing (bench.py): the group counts as one launch of kernel X
     hipEventCreate(&r.e0);
     hipEventCreate(&r.e1);
     r.flops = 0.0;
     for (int i = 0; i < count; ++i) r.flops += 2.0 * descs[i].M * (double)descs[i].N * descs[i].K;
-    r.variant = 2 * 8 + lay;
+    r.variant = p.kind * 8 + p.lay;
     g_prof_e0 = r.e0;
     g_prof_e1 = r.e1;
   }
-  switch (lay) {
-    case 0: CA_LAUNCH((XK(0, 0)), grid, block, X_LAUNCH_LDS, s, g); break;
-    case 1: CA_LAUNCH((XK(0, 1)), grid, block, X_LAUNCH_LDS, s, g); break;
-    case 2: CA_LAUNCH((XK(1, 0)), grid, block, X_LAUNCH_LDS, s, g); break;
-    default: CA_LAUNCH((XK(1, 1)), grid, block, X_LAUNCH_LDS, s, g); break;
-  }
-#undef XK
+  const int lrc = gemm_launch_plan(p, descs[0], &g, (hipStream_t)stream, "ca_gemm_bf16_group");
   if (g_prof_on) {
     g_prof_e0 = g_prof_e1 = nullptr;
     g_prof.push_back(r);
   }
-  CA_CHECK_LAUNCH("ca_gemm_bf16_group");
-  return CA_OK;
+  return lrc;
 }
 
-static int ca_gemm_launch(const CaGemmDesc* desc, void* stream) {
-  CA_CHECK_ARG(desc != nullptr, "ca_gemm_bf16: null descriptor");
-  // (a copy: the library, not the caller, owns xcd_balanced - every XCD gets the same number of tiles whenever the
-  // host said that the chip is shared with a resident kernel, ca_gemm_set_compute_cus)
-  CaGemmDesc dcopy = *desc;
-  dcopy.xcd_balanced = g_compute_cus > 0 ? 1 : 0;
-  const CaGemmDesc& d = dcopy;
-  const bool bal = dcopy.xcd_balanced != 0;
+static int gemm_validate_bf16(const CaGemmDesc& d) {
   CA_CHECK_ARG(d.A && d.B &&
                    (d.C || ((d.epilogue == CA_EPI_GELU || d.epilogue == CA_EPI_GELU_RESIDUAL) && d.C2)),
                "ca_gemm_bf16: null operand");
@@ -2699,247 +2531,35 @@ static int ca_gemm_launch(const CaGemmDesc* desc, void* stream) {
   if (d.c_sumsq)
     CA_CHECK_ARG(d.epilogue == CA_EPI_NONE && d.batch1 == 1 && d.batch2 == 1 && d.c_row_index == nullptr && d.c_split_n == 0,
                  "ca_gemm_bf16: c_sumsq needs an un-batched output with the plain epilogue");
-
-  hipStream_t s = (hipStream_t)stream;
-  const int lay = (d.a_layout ? 2 : 0) + (d.b_layout ? 1 : 0);
   CA_CHECK_ARG(d.a_layout == CA_KMAJOR || d.a_layout == CA_MNMAJOR, "ca_gemm_bf16: bad a_layout");
   CA_CHECK_ARG(d.b_layout == CA_KMAJOR || d.b_layout == CA_MNMAJOR, "ca_gemm_bf16: bad b_layout");
-  // Skinny M (greedy decoding: one token per clip): weight streaming without LDS staging.
-  // (33 .. 128 rows take it when the caller asks for what only this form has - the K|V-cache row scatter of a decoded
-  // token - or when the problem is too narrow to give the tiled kernels a grid: N < 8192 means <= 64 tiles of 128 x 128)
-  const bool skinny_wide = d.M > 32 && d.M <= 128 && d.C8 == nullptr && d.c_sumsq == nullptr &&
-                           (d.a_ln_gamma || d.c_row_index || d.c_split_n > 0 || d.N <= 8192 || d.M <= 64);
-  if (g_force_kernel == 0 && (d.M <= 32 || skinny_wide) && d.a_layout == CA_KMAJOR && d.b_layout == CA_KMAJOR && d.batch1 == 1 &&
-      d.batch2 == 1 && d.a_kseg == 0 && d.b_kseg == 0 && d.dropout_p == 0.f && d.epilogue != CA_EPI_DGELU) {
-    g_last_kind = 0;
-    CA_CHECK_ARG(d.c_split_n == 0 || (d.C_hi && (d.c_split_n % 16) == 0 && d.c_split_n < d.N && d.epilogue == CA_EPI_NONE),
-                 "ca_gemm_bf16: c_split_n needs C_hi, a multiple of 16 below N and no epilogue");
-    unsigned gy = d.M <= 32 ? 1u : (unsigned)((d.M + 31) / 32);  // row blocks of 32 (blockIdx.y)
-    // 17 .. 128 rows: 16-row workgroups over blockIdx.y wherever that leaves the launch at most four workgroups per CU
-    // (every projection of a decoder layer; not the vocabulary).  The kernel's pace is set by the requests its waves keep
-    // in flight, not by bytes: at 32 clips the 32-row form (one workgroup per column block, two row blocks against the
-    // same weight fragment - round 3) gave N = 1024 launches 64 workgroups; 16-row workgroups re-read the weights from
-    // L2 but double the waves: 3.06 -> 2.66 ms per token at 32 clips, 4.50 -> 3.90 at 64, 6.96 -> 6.60 at 128 (round 5;
-    // 64-row workgroups, the opposite direction, measured 4.40 at 64).  Same K split per output element: same bits.
-    // CA_SKINNY_MB1=0 restores 32-row workgroups.
-    static const int mb1 = [] { const char* e = getenv("CA_SKINNY_MB1"); return e ? atoi(e) : 4; }();
-    static const int mb1_rows = [] { const char* e = getenv("CA_SKINNY_MB1_ROWS"); return e ? atoi(e) : 16; }();
-    const bool rows16 = mb1 && d.M > mb1_rows && d.M > 16 && (unsigned)((d.N + 15) / 16) * gy <= (unsigned)mb1 * x_device_cus();
-    if (rows16) gy = (unsigned)((d.M + 15) / 16);
-    // columns per workgroup (round 6): the widest of 16 / 8 / 4 that still gives the launch 3/4 of a workgroup per CU
-    // (16-row workgroups only; CA_SKINNY_NT=16 restores sixteen everywhere)
-    static const int nt_force = [] { const char* e = getenv("CA_SKINNY_NT"); return e ? atoi(e) : 0; }();
-    int nt = 16;
-    if (d.M <= 16 || rows16) {
-      const unsigned want = 3u * x_device_cus() / 4u;
-      if ((unsigned)((d.N + 15) / 16) * gy < want) nt = (unsigned)((d.N + 7) / 8) * gy >= want ? 8 : 4;
-      if (nt_force == 4 || nt_force == 8 || nt_force == 16) nt = nt_force;
-    }
-    const dim3 grid((unsigned)((d.N + nt - 1) / nt), gy);
-    if (d.a_ln_gamma) {
-      CA_CHECK_ARG(d.a_ln_beta && d.K <= 2048 && ((uintptr_t)d.a_ln_gamma % 16) == 0 && ((uintptr_t)d.a_ln_beta % 16) == 0,
-                   "ca_gemm_bf16: a_ln_gamma needs a_ln_beta, K <= 2048 and 16-byte aligned vectors");
-      const int mb = (d.M <= 16 || rows16) ? 1 : 2;  // (33 .. 128 rows: 32- or 16-row blocks over blockIdx.y)
-      const int nch = (d.K + 511) / 512 <= 2 ? 2 : (d.K + 511) / 512;
-      const size_t lds = (size_t)4 * mb * 256 * sizeof(float) + (size_t)16 * mb * (d.K + SKINNY_LN_PAD) * 2;
-#define SKINNY_LN(MBV, NCHV, NTV)                                                                                    \
-  do {                                                                                                               \
-    static bool attr_ln = false;                                                                                     \
-    if (!attr_ln) {                                                                                                  \
-      hipFuncSetAttribute((const void*)ca_gemm_skinny_kernel<MBV, NCHV, 8, NTV>,                                     \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                                   \
-      attr_ln = true;                                                                                                \
-    }                                                                                                                \
-    CA_LAUNCH((ca_gemm_skinny_kernel<MBV, NCHV, 8, NTV>), grid, dim3(256), lds, s, d);                               \
-  } while (0)
-#define SKINNY_LN1(NCHV)                   \
-  do {                                     \
-    if (nt == 16) SKINNY_LN(1, NCHV, 16);  \
-    else if (nt == 8) SKINNY_LN(1, NCHV, 8); \
-    else SKINNY_LN(1, NCHV, 4);            \
-  } while (0)
-      if (mb == 1 && nch == 2) SKINNY_LN1(2);
-      else if (mb == 1 && nch == 3) SKINNY_LN1(3);
-      else if (mb == 1) SKINNY_LN1(4);
-      else if (nch == 2) SKINNY_LN(2, 2, 16);
-      else if (nch == 3) SKINNY_LN(2, 3, 16);
-      else SKINNY_LN(2, 4, 16);
-#undef SKINNY_LN1
-#undef SKINNY_LN
-    } else if (d.M <= 16 || rows16) {
-      // k-steps in flight per wave: its whole K quarter up to 32 (K = 4096: one round of loads instead of four;
-      // CA_SKINNY_U=8 restores eight)
-      static const int u_force = [] { const char* e = getenv("CA_SKINNY_U"); return e ? atoi(e) : 0; }();
-      const int per = ((d.K + 31) / 32 + 3) / 4;
-      int u = per <= 8 ? 8 : (per <= 16 ? 16 : 32);
-      if (u_force == 8 || u_force == 16 || u_force == 32) u = u_force;
-#define SKINNY_P(UV, NTV) CA_LAUNCH((ca_gemm_skinny_kernel<1, 0, UV, NTV>), grid, dim3(256), 4 * 256 * sizeof(float), s, d)
-#define SKINNY_PU(UV)            \
-  do {                           \
-    if (nt == 16) SKINNY_P(UV, 16); \
-    else if (nt == 8) SKINNY_P(UV, 8); \
-    else SKINNY_P(UV, 4);        \
-  } while (0)
-      if (u == 8) SKINNY_PU(8);
-      else if (u == 16) SKINNY_PU(16);
-      else SKINNY_PU(32);
-#undef SKINNY_PU
-#undef SKINNY_P
-    } else {
-      CA_LAUNCH((ca_gemm_skinny_kernel<2, 0>), grid, dim3(256), 8 * 256 * sizeof(float), s, d);
-    }
-    CA_CHECK_LAUNCH("ca_gemm_bf16");
-    return CA_OK;
-  }
-  CA_CHECK_ARG(!d.a_ln_gamma, "ca_gemm_bf16: a_ln_gamma exists in the skinny form only (M <= 128, K-major operands, un-batched)");
-  CA_CHECK_ARG(!d.c_row_index && d.c_split_n == 0,
-               "ca_gemm_bf16: c_row_index / c_split_n exist in the skinny form only (M <= 128, K-major operands, un-batched)");
-  // Kernel choice: the 256x128 pipelined kernel runs one workgroup per CU, so it needs enough
-  // tiles to fill the chip; small or heavily batched problems use the 128x128 kernel.
-  const int64_t nb = (int64_t)d.batch1 * d.batch2;
-  const int64_t tiles_l = (int64_t)((d.M + LBM - 1) / LBM) * ((d.N + LBN - 1) / LBN) * nb;
-  // Measured on MI355X (profiles/r01_gemm_shapes.txt): at the path's shapes (K = 1920..7680, M = 3992)
-  // the 128x128 kernel with two workgroups per CU equals or beats the 256x128 one-per-CU kernel,
-  // because its second workgroup hides the epilogue; the L kernel is kept selectable for tuning.
-  int use_l = (g_force_kernel == 2 && d.a_kseg == 0 && d.b_kseg == 0) ? 1 : 0;
-  // Kernel L (256x128, three-stage ring) takes the shapes kernel X does not fill and that give it 160 .. 768 tiles
-  // (0.4 .. 3 rounds of one workgroup per CU; CA_GEMM_L_MIN, default 100 tiles: from there it also beats the 128x128
-  // kernel on the d = 1024 models, XLS-R-300M step 19.95 -> 19.1 ms): the N = d projections and data gradients and q|k|v at the 2B shape.  Its
-  // two-tiles-ahead LDS-DMA keeps it fed under the optimiser's HBM traffic, where the 128x128 kernel (one tile ahead)
-  // loses 25 %: XLS-R-2B step 79.2 -> 76.5 ms on one box (tools/archive/exp_l3.sh).  CA_GEMM_PREFER_L=0 turns it off, a larger
-  // value widens the tile-count window (x 256).
-  static const int prefer_l = [] { const char* e = getenv("CA_GEMM_PREFER_L"); return e ? atoi(e) : 3; }();
-  // Kernel X (256x256): only where it fills the chip -- at least ~0.7 tiles per CU in its last round.
-  const int xtm = (d.M + XBM - 1) / XBM, xtn = (d.N + XBN - 1) / XBN;
-  const int64_t xt = (int64_t)xtm * xtn * nb;
-  const int64_t cus = (int64_t)x_compute_cus();  // (256 on MI355X; fewer beside a resident collective: ca_gemm_set_compute_cus)
-  const double xwaves = (double)xt / (double)cus;
-  const double xeff = xwaves / (double)((xt + cus - 1) / cus);                   // last-wave occupancy
-  const double xfill = ((double)d.M * d.N) / ((double)xtm * XBM * (double)xtn * XBN);  // tile padding waste
-  // The MN-major x MN-major (weight-gradient) form gains most from the 256x256 tile (1.0 PFLOP/s against 0.63
-  // for S inside the training step), so it switches at a lower fill than the other forms.
-  const bool tn = d.a_layout == CA_MNMAJOR && d.b_layout == CA_MNMAJOR;
-  // (thresholds from tools/dev_gemm_rule.py on the models' shapes: X wins from ~73 % occupancy of its last round
-  // - 188 / 192 / 564 tiles - and loses at 68 % - 368 tiles)
-  int use_x = (g_force_kernel == 0 && d.K >= 512 && xt >= 160 && xeff * xfill >= (tn ? 0.60 : 0.70)) ? 1 : 0;
-  if (g_force_kernel == 3 || d.a_colsum) use_x = 1;  // the column sums live in kernel X only
-  static const int l_over_x = [] { const char* e = getenv("CA_GEMM_L_OVER_X"); return e ? atoi(e) : 0; }();
-  static const int l_min = [] { const char* e = getenv("CA_GEMM_L_MIN"); return e ? atoi(e) : 100; }();
-  if (prefer_l && g_force_kernel == 0 && d.a_kseg == 0 && d.b_kseg == 0 && d.K >= 512 && tiles_l >= l_min &&
-      (tiles_l <= cus * prefer_l || (use_x && l_over_x)) && !d.a_colsum &&
-      (!use_x || (l_over_x == 1 && !tn) || l_over_x == 2 || (l_over_x == 3 && lay == 0))) {
-    use_l = 1;
-    use_x = 0;
-  }
-  // Beside a resident kernel that holds some CUs (ca_gemm_set_compute_cus(n), n below the chip's count) the rules above -
-  // tuned for exactly 256 CUs - pick single-round tilings that then run TWO rounds (240 tiles on 224 CUs).  There the
-  // choice is made by counting rounds on the CUs that are left: cost = rounds x tile work / the shape's efficiency, in
-  // units of one 128 x 128 tile's work (kernel S: two tiles per CU at a time; efficiencies from
-  // profiles/r05_gemm_shapes.txt, weight-gradient form in brackets): X 4 / 1.0, L 2 / 0.93 [0.85], S 2 / 0.8 [0.6] per
-  // pair, M 1 / 0.6.  tenant_kind: -1 = not in this regime.
-  int tenant_kind = -1;
-  if (g_force_kernel == 0 && g_compute_cus > 0 && cus < (int64_t)x_device_cus() && nb == 1 && d.a_kseg == 0 && d.b_kseg == 0 &&
-      d.K >= 512 && !d.a_colsum && d.M > 128) {
-    const int64_t ts = (int64_t)((d.M + BM - 1) / BM) * ((d.N + BN - 1) / BN);
-    auto rounds = [](int64_t tiles, int64_t slots) { return (double)((tiles + slots - 1) / slots); };
-    const double cx = rounds(xt, cus) * 4.0, cl = rounds(tiles_l, cus) * 2.0 / (tn ? 0.85 : 0.93),
-                 cs = rounds(ts, 2 * cus) * 2.0 / (tn ? 0.6 : 0.8), cm = rounds(ts, cus) * 1.0 / 0.6;
-    tenant_kind = 2;
-    double best = cx;
-    if (cl < best) { best = cl; tenant_kind = 1; }
-    if (cs < best) { best = cs; tenant_kind = 0; }
-    if (cm < best) { best = cm; tenant_kind = 3; }
-    use_x = tenant_kind == 2;
-    use_l = tenant_kind == 1;
-  }
-  g_last_kind = use_x ? 2 : (use_l ? 1 : 0);
-  if (use_x) {
-    static bool xattr = false;
-    const bool ks = d.a_kseg > 0 || d.b_kseg > 0;
-#define XK(a, b, k) ca_gemm_kernel_x<a, b, k>
-    if (!xattr) {
-      const void* fs[8] = {(const void*)XK(0, 0, false), (const void*)XK(0, 1, false), (const void*)XK(1, 0, false),
-                           (const void*)XK(1, 1, false), (const void*)XK(0, 0, true),  (const void*)XK(0, 1, true),
-                           (const void*)XK(1, 0, true),  (const void*)XK(1, 1, true)};
-      for (int i = 0; i < 8; ++i) hipFuncSetAttribute(fs[i], hipFuncAttributeMaxDynamicSharedMemorySize, X_LAUNCH_LDS);
-      xattr = true;
-    }
-    dim3 grid, block(512);
-    CaGemmGroup one;
-    one.d[0] = d;
-    one.count = 0;
-    one.first[0] = 0;
-    one.total = 0;
-    x_launch_geometry(one, tile_grid<4, 8>(xtm, xtn, bal), (unsigned)nb, grid);
-    switch (lay + (ks ? 4 : 0)) {
-      case 0: CA_LAUNCH((XK(0, 0, false)), grid, block, X_LAUNCH_LDS, s, one); break;
-      case 1: CA_LAUNCH((XK(0, 1, false)), grid, block, X_LAUNCH_LDS, s, one); break;
-      case 2: CA_LAUNCH((XK(1, 0, false)), grid, block, X_LAUNCH_LDS, s, one); break;
-      case 3: CA_LAUNCH((XK(1, 1, false)), grid, block, X_LAUNCH_LDS, s, one); break;
-      case 4: CA_LAUNCH((XK(0, 0, true)), grid, block, X_LAUNCH_LDS, s, one); break;
-      case 5: CA_LAUNCH((XK(0, 1, true)), grid, block, X_LAUNCH_LDS, s, one); break;
-      case 6: CA_LAUNCH((XK(1, 0, true)), grid, block, X_LAUNCH_LDS, s, one); break;
-      default: CA_LAUNCH((XK(1, 1, true)), grid, block, X_LAUNCH_LDS, s, one); break;
-    }
-#undef XK
-    CA_CHECK_LAUNCH("ca_gemm_bf16");
-    return CA_OK;
-  }
-  if (use_l) {
-    static bool attr_done = false;
-    if (!attr_done) {
-      hipFuncSetAttribute((const void*)ca_gemm_kernel_l<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, L_LDS_BYTES);
-      hipFuncSetAttribute((const void*)ca_gemm_kernel_l<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, L_LDS_BYTES);
-      hipFuncSetAttribute((const void*)ca_gemm_kernel_l<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, L_LDS_BYTES);
-      hipFuncSetAttribute((const void*)ca_gemm_kernel_l<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, L_LDS_BYTES);
-      attr_done = true;
-    }
-    dim3 grid(tile_grid<4, 8>((d.M + LBM - 1) / LBM, (d.N + LBN - 1) / LBN, bal), 1, (unsigned)nb);
-    dim3 block(512);
-    switch (lay) {
-      case 0: CA_LAUNCH((ca_gemm_kernel_l<0, 0>), grid, block, L_LDS_BYTES, s, d); break;
-      case 1: CA_LAUNCH((ca_gemm_kernel_l<0, 1>), grid, block, L_LDS_BYTES, s, d); break;
-      case 2: CA_LAUNCH((ca_gemm_kernel_l<1, 0>), grid, block, L_LDS_BYTES, s, d); break;
-      default: CA_LAUNCH((ca_gemm_kernel_l<1, 1>), grid, block, L_LDS_BYTES, s, d); break;
-    }
-  } else {
-    const int ntm = (d.M + BM - 1) / BM, ntn = (d.N + BN - 1) / BN;
-    dim3 grid(tile_grid<8, 8>(ntm, ntn, bal), 1, (unsigned)nb);
-    dim3 block(256);
-    const size_t lds = LDS_BYTES;
-    const bool ks = d.a_kseg > 0 || d.b_kseg > 0;
-    // at most one tile per CU: kernel M (two waves per SIMD on the same tile; CA_GEMM_M=0 switches it off)
-    static const int m_max = [] { const char* e = getenv("CA_GEMM_M"); return e ? atoi(e) : 256; }();
-    if (!ks && (g_force_kernel == 5 || tenant_kind == 3 ||
-                (g_force_kernel == 0 && tenant_kind < 0 && (int64_t)ntm * ntn * nb <= m_max && d.K >= 2 * BK))) {
-      static bool mattr = false;
-      if (!mattr) {
-        const void* fs[4] = {(const void*)ca_gemm_kernel_m<0, 0>, (const void*)ca_gemm_kernel_m<0, 1>,
-                             (const void*)ca_gemm_kernel_m<1, 0>, (const void*)ca_gemm_kernel_m<1, 1>};
-        for (int i = 0; i < 4; ++i) hipFuncSetAttribute(fs[i], hipFuncAttributeMaxDynamicSharedMemorySize, M_LDS_BYTES);
-        mattr = true;
-      }
-      const dim3 mblock(512);
-      switch (lay) {
-        case 0: CA_LAUNCH((ca_gemm_kernel_m<0, 0>), grid, mblock, M_LDS_BYTES, s, d); break;
-        case 1: CA_LAUNCH((ca_gemm_kernel_m<0, 1>), grid, mblock, M_LDS_BYTES, s, d); break;
-        case 2: CA_LAUNCH((ca_gemm_kernel_m<1, 0>), grid, mblock, M_LDS_BYTES, s, d); break;
-        default: CA_LAUNCH((ca_gemm_kernel_m<1, 1>), grid, mblock, M_LDS_BYTES, s, d); break;
-      }
-      CA_CHECK_LAUNCH("ca_gemm_bf16");
-      return CA_OK;
-    }
-    switch (lay + (ks ? 4 : 0)) {
-      case 0: CA_LAUNCH((ca_gemm_kernel<0, 0, false>), grid, block, lds, s, d); break;
-      case 1: CA_LAUNCH((ca_gemm_kernel<0, 1, false>), grid, block, lds, s, d); break;
-      case 2: CA_LAUNCH((ca_gemm_kernel<1, 0, false>), grid, block, lds, s, d); break;
-      case 3: CA_LAUNCH((ca_gemm_kernel<1, 1, false>), grid, block, lds, s, d); break;
-      case 4: CA_LAUNCH((ca_gemm_kernel<0, 0, true>), grid, block, lds, s, d); break;
-      case 5: CA_LAUNCH((ca_gemm_kernel<0, 1, true>), grid, block, lds, s, d); break;
-      case 6: CA_LAUNCH((ca_gemm_kernel<1, 0, true>), grid, block, lds, s, d); break;
-      default: CA_LAUNCH((ca_gemm_kernel<1, 1, true>), grid, block, lds, s, d); break;
-    }
-  }
-  CA_CHECK_LAUNCH("ca_gemm_bf16");
   return CA_OK;
+}
+// what the skinny form asks of the features only it has
+static int gemm_validate_skinny(const CaGemmDesc& d) {
+  CA_CHECK_ARG(d.c_split_n == 0 || (d.C_hi && (d.c_split_n % 16) == 0 && d.c_split_n < d.N && d.epilogue == CA_EPI_NONE),
+               "ca_gemm_bf16: c_split_n needs C_hi, a multiple of 16 below N and no epilogue");
+  if (d.a_ln_gamma)
+    CA_CHECK_ARG(d.a_ln_beta && d.K <= 2048 && ((uintptr_t)d.a_ln_gamma % 16) == 0 && ((uintptr_t)d.a_ln_beta % 16) == 0,
+                 "ca_gemm_bf16: a_ln_gamma needs a_ln_beta, K <= 2048 and 16-byte aligned vectors");
+  return CA_OK;
+}
+
+static int ca_gemm_launch(const CaGemmDesc* desc, void* stream) {
+  CA_CHECK_ARG(desc != nullptr, "ca_gemm_bf16: null descriptor");
+  const GemmKnobs knobs = gemm_knobs();
+  // (a copy: the library, not the caller, owns xcd_balanced - every XCD gets the same number of tiles whenever the
+  // host said that the chip is shared with a resident kernel, ca_gemm_set_compute_cus)
+  CaGemmDesc d = *desc;
+  d.xcd_balanced = knobs.compute_cus > 0 ? 1 : 0;
+  int rc = gemm_validate_bf16(d);
+  if (rc != CA_OK) return rc;
+  const GemmPlan p = gemm_plan_bf16(d, knobs);
+  CA_CHECK_ARG(p.error != GEMM_PLAN_LN_NOT_SKINNY,
+               "ca_gemm_bf16: a_ln_gamma exists in the skinny form only (M <= 128, K-major operands, un-batched)");
+  CA_CHECK_ARG(p.error != GEMM_PLAN_ROWS_NOT_SKINNY,
+               "ca_gemm_bf16: c_row_index / c_split_n exist in the skinny form only (M <= 128, K-major operands, un-batched)");
+  g_last_kind = p.kind;
+  if (p.family == GEMM_SKINNY && (rc = gemm_validate_skinny(d)) != CA_OK) return rc;
+  return gemm_launch_plan(p, d, nullptr, (hipStream_t)stream, "ca_gemm_bf16");
 }

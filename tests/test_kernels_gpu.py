@@ -973,3 +973,66 @@ def test_gemm_results_do_not_depend_on_the_compute_cu_setting(ops, M, N, K, al, 
     finally:
         lib.ca_gemm_set_compute_cus(0)
         torch.cuda.synchronize()
+
+
+def _plan_rows_one_per_kernel():
+    """From tests/golden/gemm_plan.json: for every kernel family, and for every skinny variant (row blocks, LayerNorm
+    prologue or not, k-steps in flight, columns per workgroup), the smallest plain ca_gemm_bf16 problem that the
+    automatic choice - default knobs, the whole 256-CU chip - sends there.  The 256x256 row is the smallest product
+    M N (at K = 512, weight-gradient form) its fill rule accepts."""
+    import json
+    from pathlib import Path
+
+    t = json.loads((Path(__file__).parent / "golden" / "gemm_plan.json").read_text())
+    c = {k: i for i, k in enumerate(t["columns"])}
+    default = dict(x_persist=1, skinny_mb1=4, skinny_mb1_rows=16, skinny_nt=0, skinny_u=0, prefer_l=3, l_over_x=0, l_min=100,
+                   m_max=256, force_kernel=0, compute_cus=0, device_cus=256, api=0, batch1=1, batch2=1)
+    plain = ("a_kseg", "b_kseg", "epilogue", "dropout", "a_colsum", "c_row_index", "c_split_n", "C8", "c_sumsq", "error")
+    best = {}
+    for r in t["rows"]:
+        if any(r[c[k]] != v for k, v in default.items()) or any(r[c[k]] for k in plain):
+            continue
+        key = (r[c["family"]], r[c["mb"]], min(r[c["nch"]], 1), r[c["u"]], r[c["nt"]])
+        if key not in best or r[c["M"]] * r[c["N"]] * r[c["K"]] < best[key]["M"] * best[key]["N"] * best[key]["K"]:
+            best[key] = {k: r[i] for k, i in c.items()}
+    assert {k[0] for k in best} == {0, 1, 2, 3, 4} and 10 <= len(best) <= 16, sorted(best)
+    return [best[k] for k in sorted(best)]
+
+
+@pytest.mark.parametrize("row", _plan_rows_one_per_kernel(),
+                         ids=lambda r: "fam{family}_mb{mb}_nch{nch}_u{u}_nt{nt}".format(**r))
+def test_gemm_automatic_choice_fires_the_planned_kernel(ops, row):
+    """One launch per kernel family and skinny variant with automatic choice: the profiler's variant index that fired is
+    the table's (kind * 8 + segmented * 4 + layout), and the result is torch.matmul's within test_gemm_layouts' bound
+    (tiled kernels) / test_skinny_gemm_matches_torch's bound (skinny form; with the LayerNorm prologue the reference
+    operand is ca_layernorm_fwd's output, which the prologue reproduces bit for bit)."""
+    assert torch.cuda.get_device_properties(0).multi_processor_count == 256, "the table's default rows are for a 256-CU device"
+    M, N, K, al, bl = row["M"], row["N"], row["K"], row["a_layout"], row["b_layout"]
+    skinny = row["family"] == 0
+    g = torch.Generator(device=DEV).manual_seed(M * 1000 + N)
+    Mp, Np, Kp = (M + 7) // 8 * 8, (N + 7) // 8 * 8, (K + 7) // 8 * 8
+    A = torch.zeros(Mp, Kp, dtype=torch.bfloat16, device=DEV)  # (zero padding: rows / k beyond the problem are readable)
+    B = torch.zeros(Np, Kp, dtype=torch.bfloat16, device=DEV)
+    A[:M, :K] = bf(torch.randn(M, K, generator=g, device=DEV) * 0.5)
+    B[:N, :K] = bf(torch.randn(N, K, generator=g, device=DEV) * (0.05 if skinny else 0.5))
+    Ad = A.t().contiguous() if al else A
+    Bd = B.t().contiguous() if bl else B
+    kw = {}
+    Aref = A[:M, :K]
+    if row["a_ln"]:
+        gamma, beta = torch.rand(K, generator=g, device=DEV) + 0.5, torch.randn(K, generator=g, device=DEV)
+        Aref = torch.zeros(M, K, dtype=torch.bfloat16, device=DEV)
+        ops.layernorm_fwd(A[:M, :K].contiguous(), gamma, beta, Aref, None, M, K, 1e-5)
+        kw["a_ln"] = (gamma, beta, 1e-5)
+    ref = torch.matmul(Aref.float(), B[:N, :K].float().t())
+    C = torch.zeros(M, Np, dtype=torch.float32, device=DEV)
+    ops.prof_begin()
+    try:
+        ops.gemm(Ad, Bd, C, M=M, N=N, K=K, lda=(Mp if al else Kp), ldb=(Np if bl else Kp), ldc=Np, a_layout=al, b_layout=bl, **kw)
+    finally:
+        fired = [i for i, p in enumerate(ops.prof_end()) if p["count"]]
+    assert fired == [row["kind"] * 8 + row["ks"] * 4 + row["lay"]], (fired, row)
+    err = (C[:, :N] - ref).abs().max().item()
+    bound = 2e-3 * max(1.0, float(ref.abs().max())) if skinny else 1e-3 * (K ** 0.5)
+    print(f"plan row M {M} N {N} K {K} family {row['family']}: variant {fired}, max |err| {err:.3e}, bound {bound:.3e}")
+    assert err <= bound, (err, bound)

@@ -69,29 +69,88 @@ def transcribe(model, processor, arrays: list, batch_size: int = 16, chunk_lengt
 
 
 def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max_length: int | None = None,
-                       num_beams: int = 1):
+                       num_beams: int = 1, return_timestamps: bool = False):
     """The Whisper branch of the ASR pipeline ($TF/pipelines/automatic_speech_recognition.py:345,529,600): pad / trim
     every clip to 30 s, log-mel on the GPU, `model.generate(input_features, language="danish", task="transcribe")`
     (R/src/coral/evaluate.py:56-60), decode the generated ids without special tokens.
     -> (texts, id rows).  Without the byte-level BPE files (offline) the texts are the ids rendered as words.
     num_beams >= 2: beam search (`generate_kwargs={"num_beams": k}` of the pipeline); a batch is then decoded at most
-    128 // num_beams clips at a time (the decoder's row limit)."""
+    128 // num_beams clips at a time (the decoder's row limit).
+    A clip longer than 30 s is not cut: it goes through the sequential long-form loop of transformers' `generate`
+    (coral_amd/longform_whisper.py: windows of 30 s decoded with timestamps, each starting where the last closed
+    segment of the one before ended) and its segments are stitched to one text; its id row is the segments' ids in
+    order, timestamps included.  return_timestamps=True: every clip takes that loop and the first result is a list of
+    {"text", "chunks": [{"text", "timestamp": (start_s, end_s)}]}.  Both are greedy only."""
     model.eval()
     texts, rows = [], []
     max_length = int(max_length or model.shape.max_target_positions)
     num_beams = int(num_beams or 1)
     if num_beams < 1:
         raise ValueError(f"num_beams must be a positive integer, got {num_beams}")
+    from .whisper import N_SAMPLES
+
+    if return_timestamps not in (True, False, None):
+        raise ValueError(f"return_timestamps must be true or false for a Whisper model, got {return_timestamps!r}")
+    looped = [i for i, a in enumerate(arrays) if return_timestamps or len(a) > N_SAMPLES]
+    if looped and num_beams > 1:
+        raise ValueError(f"num_beams={num_beams}: return_timestamps / recordings longer than 30 s are decoded greedily "
+                         "only (beam search with timestamps is not implemented)")
+    taken = set(looped)
+    plain = [i for i in range(len(arrays)) if i not in taken]
     gen_kw = dict(num_beams=num_beams) if num_beams > 1 else {}
     if num_beams > 1:
         batch_size = max(1, min(batch_size, 128 // num_beams))
-    for i in range(0, len(arrays), batch_size):
-        feats = processor.feature_extractor(arrays[i:i + batch_size], sampling_rate=processor.feature_extractor.sampling_rate)
+    for i in range(0, len(plain), batch_size):
+        feats = processor.feature_extractor([arrays[j] for j in plain[i:i + batch_size]],
+                                            sampling_rate=processor.feature_extractor.sampling_rate)
         ids = model.generate(feats, language="danish", task="transcribe", max_length=max_length, **gen_kw)
         ids = ids.tolist() if hasattr(ids, "tolist") else [list(map(int, r)) for r in ids]
         rows += ids
         texts += processor.batch_decode(ids, skip_special_tokens=True)
-    return texts, rows
+    if not looped:
+        return texts, rows
+    # back into the order of `arrays`
+    results, all_rows = [None] * len(arrays), [None] * len(arrays)
+    for i, t, r in zip(plain, texts, rows):
+        results[i], all_rows[i] = t, r
+    timed, timed_rows = _transcribe_whisper_windows(model, processor, [arrays[i] for i in looped], batch_size, max_length,
+                                                    bool(return_timestamps))
+    for i, t, r in zip(looped, timed, timed_rows):
+        results[i], all_rows[i] = t, r
+    return results, all_rows
+
+
+def _transcribe_whisper_windows(model, processor, arrays, batch_size, max_length, return_timestamps):
+    """The long-form loop over `arrays` (clips above 30 s, or every clip when timestamps are asked for), all of them
+    sharing its rounds.  -> (texts, or {"text", "chunks"} per clip with return_timestamps; id rows)."""
+    from .longform_whisper import run_longform, stitched_ids
+    from .whisper import N_SAMPLES
+
+    fe = processor.feature_extractor
+    prefix_len, tb = len(model.forced_prefix(return_timestamps=True)), model.forced_prefix()[-1] + 1
+    # a clip of at most 30 s is padded to 30 s before the log-mel, as the pipeline's extractor pads it; a longer one
+    # keeps its length (truncation=False) and its own maximum
+    mels = [fe(a, sampling_rate=fe.sampling_rate)[0] if len(a) <= N_SAMPLES else fe.whole(a) for a in arrays]
+
+    def window_generate(batch):
+        feats = torch.stack([torch.nn.functional.pad(mels[c][:, seek:seek + 3000], (0, max(0, 3000 - (mels[c].shape[1] - seek))))
+                             for c, seek in batch])
+        return model.generate(feats, language="danish", task="transcribe", max_length=max_length, return_timestamps=True)
+
+    s = model.shape
+    done = run_longform(window_generate, [m.shape[1] for m in mels], tb, prefix_len, s.pad_token_id, s.eos_token_id,
+                        batch_size=batch_size)
+    results, rows = [], []
+    for res in done:
+        rows.append([t for _, _, ids in res["segments"] for t in ids])
+        text = processor.batch_decode([stitched_ids(res["segments"], tb)], skip_special_tokens=True)[0]
+        if return_timestamps:
+            chunks = [dict(text=processor.batch_decode([[t for t in ids if t < tb]], skip_special_tokens=True)[0],
+                           timestamp=(start, end)) for start, end, ids in res["segments"]]
+            results.append(dict(text=text, chunks=chunks))
+        else:
+            results.append(text)
+    return results, rows
 
 
 def saved_model_type(model_dir) -> str:
@@ -118,8 +177,9 @@ def evaluate(config, examples: list | None = None) -> dict:
     mtype = saved_model_type(model_dir)
     chunk_length_s = config.get("chunk_length_s", 0) or 0
     if mtype == "whisper" and chunk_length_s > 0:
-        raise ValueError("chunk_length_s > 0 is built for wav2vec2 models only (Whisper long-form decoding is not): "
-                         "set chunk_length_s to 0")
+        raise ValueError("chunk_length_s > 0 is built for wav2vec2 models only: a Whisper model transcribes recordings "
+                         "longer than 30 s without it (transformers' sequential long-form decoding; the pipeline's chunked "
+                         "merge is not built): set chunk_length_s to 0")
     mcfg = DictConfig(model=DictConfig(type=mtype, sampling_rate=config.sampling_rate, decoder=None),
                       model_dir=model_dir, padding="longest",
                       max_seconds_per_example=config.max_seconds_per_example)
@@ -127,7 +187,7 @@ def evaluate(config, examples: list | None = None) -> dict:
     # `no_lm` (R/src/coral/evaluate.py:123-158): false decodes with model_dir/language_model/ when there is one
     saved = setup.load_saved() if mtype == "whisper" else setup.load_saved(no_lm=bool(config.get("no_lm", False)))
     model, processor = saved.model, saved.processor
-    id_rows = None
+    id_rows = timed = None
     if mtype == "whisper":
         if examples is None:
             import numpy as np
@@ -139,7 +199,10 @@ def evaluate(config, examples: list | None = None) -> dict:
                 w = np.clip(0.1 * rng.randn(n), -1, 1).astype(np.float32)
                 examples.append(dict(audio=w / np.abs(w).max(), text=""))
         preds, id_rows = transcribe_whisper(model, processor, [e["audio"] for e in examples], config.batch_size,
-                                            config.get("generation_max_length", None), config.get("num_beams", 1) or 1)
+                                            config.get("generation_max_length", None), config.get("num_beams", 1) or 1,
+                                            return_timestamps=bool(config.get("return_timestamps", False) or False))
+        if preds and isinstance(preds[0], dict):
+            timed, preds = preds, [p["text"] for p in preds]
     else:
         if examples is None:
             examples = [dict(audio=ex["input_values"], text=ex["text"])
@@ -166,4 +229,6 @@ def evaluate(config, examples: list | None = None) -> dict:
         scores["csv"] = str(path)
     if id_rows is not None:
         scores["token_ids"] = id_rows
+    if timed is not None:
+        scores["chunks"] = [p["chunks"] for p in timed]
     return scores

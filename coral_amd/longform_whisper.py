@@ -1,0 +1,125 @@
+"""Whisper timestamps on the host: segments of a decoded window and the sequential long-form loop.
+
+Restated from the installed transformers ($TF/models/whisper/generation_whisper.py), not imported from it:
+
+  * `segments_of`  - `_retrieve_segment`: a window's generated ids are cut at every closed timestamp pair; the window
+    then advances to the last closed pair, or by all its frames when it ends in a single timestamp or holds no pair;
+  * `run_longform` - the loop of `WhisperGenerationMixin.generate` for inputs above 3000 frames with the arguments the
+    ASR pipeline passes (R/src/coral/evaluate.py runs `pipeline(...)` with no generate_kwargs): no temperature
+    fallback, no `condition_on_prev_tokens`, no no-speech / log-prob / compression thresholds, no prompt.  Every clip
+    keeps a `seek` (in frames of 10 ms); each round decodes the window [seek, seek + 3000) of every unfinished clip as
+    one batch.  What decodes a batch of windows is a parameter, so the loop itself needs no GPU.
+
+Times are float64 seconds computed as transformers computes them: offset = seek * time_precision / input_stride,
+time = offset + timestamp_index * time_precision."""
+from __future__ import annotations
+
+import numpy as np
+
+TIME_PRECISION = 0.02           # seconds per timestamp step (= one encoder position)
+TIME_PRECISION_FEATURES = 0.01  # seconds per log-mel frame
+INPUT_STRIDE = 2                # log-mel frames per encoder position
+WINDOW_FRAMES = 3000
+
+# arguments of transformers' long-form generate that change what the loop does and that this build does not implement
+_LONGFORM_REFUSED = {"temperature": (None, 0.0, 1.0), "condition_on_prev_tokens": (None, False),
+                     "no_speech_threshold": (None,), "logprob_threshold": (None,), "compression_ratio_threshold": (None,),
+                     "prompt_ids": (None,), "prompt_condition_type": (None,), "return_token_timestamps": (None, False),
+                     "num_beams": (None, 1)}
+
+
+def check_longform_arguments(other: dict) -> None:
+    for name, val in other.items():
+        neutral = _LONGFORM_REFUSED.get(name)
+        if neutral is None:
+            raise ValueError(f"long-form decoding: argument {name}={val!r} is not known to this build")
+        if not any(val is n or (n is not None and type(val) is type(n) and val == n) for n in neutral):
+            raise ValueError(f"long-form decoding: {name}={val!r} is not implemented (greedy windows, each decoded from the "
+                             "forced prefix alone)")
+
+
+def strip_generated(row, prefix_len: int, pad_id: int, eos_id: int) -> list[int]:
+    """A generated row -> the tokens after the prefix without the padding and the EOS (`generate_with_fallback`:
+    'remove all padding tokens, except for the eos token', then 'remove eos token')."""
+    gen = [int(t) for t in row[prefix_len:]]
+    if gen and gen[-1] == pad_id:
+        n = sum(1 for t in gen if t == pad_id) - (1 if pad_id == eos_id else 0)
+        if n:
+            gen = gen[:-n]
+    if gen and gen[-1] == eos_id:
+        gen = gen[:-1]
+    return gen
+
+
+def segments_of(ids, timestamp_begin: int, time_precision: float = TIME_PRECISION, num_frames: int = WINDOW_FRAMES,
+                time_offset: float = 0.0, return_advance: bool = False):
+    """ids: the tokens one window generated (no prefix, no EOS).  -> [(start_s, end_s, token ids)] as `_retrieve_segment`
+    cuts them (a segment's ids keep its timestamp tokens); return_advance=True: (segments, frames to advance by)."""
+    ids = [int(t) for t in ids]
+    is_ts = [t >= timestamp_begin for t in ids]
+    single_ending = is_ts[-2:] == [False, True]
+    slices = [i + 1 for i in range(len(ids) - 1) if is_ts[i] and is_ts[i + 1]]
+    segments = []
+    if slices:
+        if single_ending:
+            slices.append(len(ids))
+        else:
+            slices[-1] += 1  # the last segment keeps its closing timestamp and the one that opens the unfinished rest
+        last = 0
+        for i, cur in enumerate(slices):
+            tokens = ids[last:cur]
+            is_last = i == len(slices) - 1
+            start = tokens[0] - timestamp_begin
+            end = tokens[-1 if (not is_last or single_ending) else -2] - timestamp_begin
+            segments.append((time_offset + float(start) * time_precision, time_offset + float(end) * time_precision, tokens))
+            last = cur
+        if single_ending:
+            advance = num_frames  # no speech after the last timestamp
+        else:
+            advance = (ids[last - 2] - timestamp_begin) * INPUT_STRIDE  # the unfinished rest is decoded again
+    else:
+        stamps = [t for t in ids if t >= timestamp_begin]
+        # (transformers multiplies a 0-dim integer tensor by Python floats here: the arithmetic is float32)
+        last_pos = int(np.float32(num_frames) * np.float32(TIME_PRECISION_FEATURES) / np.float32(time_precision))
+        if stamps and stamps[-1] != timestamp_begin:
+            last_pos = float(stamps[-1] - timestamp_begin)
+        segments.append((time_offset, time_offset + last_pos * time_precision, ids))
+        advance = num_frames
+    return (segments, int(advance)) if return_advance else segments
+
+
+def run_longform(window_generate, num_frames, timestamp_begin: int, prefix_len: int, pad_id: int, eos_id: int,
+                 time_precision: float = TIME_PRECISION, batch_size: int | None = None, **other):
+    """window_generate([(clip, seek), ...]) -> one generated id row per entry (prefix included, padded as `generate`
+    pads).  num_frames: log-mel frames per clip.  -> per clip dict(segments=[(start_s, end_s, ids)], windows=[(seek,
+    generated ids)]).  batch_size: at most that many windows per call (None: all unfinished clips at once)."""
+    check_longform_arguments(other)
+    num_frames = [int(n) for n in num_frames]
+    seek = [0] * len(num_frames)
+    out = [dict(segments=[], windows=[]) for _ in num_frames]
+    while True:
+        todo = [i for i, n in enumerate(num_frames) if seek[i] < n]
+        if not todo:
+            return out
+        step = batch_size or len(todo)
+        for a in range(0, len(todo), step):
+            batch = todo[a:a + step]
+            rows = window_generate([(i, seek[i]) for i in batch])
+            if len(rows) != len(batch):
+                raise ValueError(f"window_generate returned {len(rows)} rows for {len(batch)} windows")
+            for i, row in zip(batch, rows):
+                gen = strip_generated(row, prefix_len, pad_id, eos_id)
+                frames = min(num_frames[i] - seek[i], WINDOW_FRAMES)
+                offset = seek[i] * time_precision / INPUT_STRIDE
+                out[i]["windows"].append((seek[i], gen))
+                if not gen:  # (cannot happen under the timestamp rules: the first token is a timestamp)
+                    seek[i] += frames
+                    continue
+                segs, adv = segments_of(gen, timestamp_begin, time_precision, frames, offset, return_advance=True)
+                out[i]["segments"] += segs
+                seek[i] += adv
+
+
+def stitched_ids(segments, timestamp_begin: int) -> list[int]:
+    """The text tokens of a recording's segments in order (timestamps dropped)."""
+    return [t for _, _, ids in segments for t in ids if t < timestamp_begin]

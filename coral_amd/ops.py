@@ -729,6 +729,31 @@ def argmax_advance(logits, suppress, out, rows, V, ldv, done, ids, tok, pos, kle
                                   _p(tok), _p(pos), _p(klen), int(pad_id), int(eos_id), _stream()), "ca_argmax_advance")
 
 
+def _cap(max_initial_timestamp_index):
+    return -1 if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
+
+
+def argmax_timestamps(logits, suppress, out, rows, V, ldv, ids, pos, begin_index, timestamp_begin, eos_id,
+                      max_initial_timestamp_index=None):
+    """argmax_masked under Whisper's timestamp rules; the history of row r is ids[r, begin_index : pos[r] + 1]."""
+    if ids.dtype != torch.int64 or ids.dim() != 2 or ids.stride(1) != 1 or pos.dtype != torch.int32:
+        raise CoralAmdError("argmax_timestamps: ids must be a row-major int64 matrix, pos int32")
+    check(lib().ca_argmax_timestamps(_p(logits), _p(suppress), _p(out), rows, V, ldv, _p(ids), ids.stride(0), _p(pos),
+                                     int(begin_index), int(timestamp_begin), int(eos_id),
+                                     _cap(max_initial_timestamp_index), _stream()), "ca_argmax_timestamps")
+
+
+def argmax_timestamps_advance(logits, suppress, out, rows, V, ldv, done, ids, tok, pos, klen, pad_id, eos_id, begin_index,
+                              timestamp_begin, max_initial_timestamp_index=None):
+    """argmax_timestamps + the bookkeeping of argmax_advance (ids / pos are the history and the state it moves)."""
+    if done.dtype != torch.bool or ids.dtype != torch.int64 or ids.dim() != 2 or ids.stride(1) != 1:
+        raise CoralAmdError("argmax_timestamps_advance: done must be bool, ids a row-major int64 matrix")
+    check(lib().ca_argmax_timestamps_advance(_p(logits), _p(suppress), _p(out), rows, V, ldv, done.data_ptr(), _p(ids),
+                                             ids.stride(0), _p(tok), _p(pos), _p(klen), int(pad_id), int(eos_id),
+                                             int(begin_index), int(timestamp_begin), _cap(max_initial_timestamp_index),
+                                             _stream()), "ca_argmax_timestamps_advance")
+
+
 def beam_select_workspace_bytes(B, k, V):
     return lib().ca_beam_select_workspace_bytes(B, k, V)
 

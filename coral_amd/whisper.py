@@ -267,7 +267,8 @@ class WhisperEngine:
 
     # ---- front end ---------------------------------------------------------------------------
     def log_mel(self, waves: torch.Tensor) -> torch.Tensor:
-        """waves f32 [B, 480000] (padded/truncated PCM) -> input_features f32 [B, mels, 3000] on the GPU."""
+        """waves f32 [B, N] (480000 = PCM padded / truncated to 30 s; any multiple of 160 for a whole recording) ->
+        input_features f32 [B, mels, N / 160] on the GPU."""
         B, N = waves.shape
         x = waves.to(self.device, torch.float32).contiguous()
         out = torch.empty(B, self.s.num_mel_bins, N // HOP, dtype=torch.float32, device=self.device)
@@ -527,9 +528,14 @@ class WhisperEngine:
 
     def _persistent_state(self, cache: dict, g: dict, suppress: torch.Tensor):
         """Descriptor + device tables of ca_whisper_decode_token for this decode state, or None where the launch
-        sequence stays (shape / device outside the kernel's limits, CA_DECODE_PERSISTENT=0)."""
+        sequence stays (shape / device outside the kernel's limits, CA_DECODE_PERSISTENT=0).  Decoding with timestamps
+        (g["ts"]) always keeps the launch sequence: the one-launch kernel's pick is the plain masked argmax
+        (csrc/decode.hip), the timestamp rules live in ca_argmax_timestamps_advance."""
         if "persist" in g:
             return g["persist"]
+        if g.get("ts") is not None:
+            g["persist"] = None
+            return None
         s, st = self.s, self.store
         B, Lmax = cache["B"], cache["max_len"]
         d, f, H, V = s.d_model, s.decoder_ffn_dim, s.decoder_attention_heads, s.vocab_size
@@ -659,6 +665,11 @@ class WhisperEngine:
         V, Vp = s.vocab_size, _r8(s.vocab_size)
         # argmax + the step's bookkeeping in one launch: out[b, pos + 1] = the token (pad for finished rows), done |= eos,
         # tok = the token, pos += 1, klen += 1
+        if g.get("ts") is not None:  # the same step under the timestamp rules (history: g["out"] up to g["pos"])
+            begin, tb, cap = g["ts"]
+            ops.argmax_timestamps_advance(g["logits"], suppress, g["nxt"], B, V, Vp, g["done"], g["out"], g["tok"], g["pos"],
+                                          g["klen"], g["pad_id"], g["eos"], begin, tb, cap)
+            return
         ops.argmax_advance(g["logits"], suppress, g["nxt"], B, V, Vp, g["done"], g["out"], g["tok"], g["pos"], g["klen"],
                            g["pad_id"], g["eos"])
 
@@ -686,14 +697,30 @@ class WhisperEngine:
     def generate(self, input_features, prefix: list[int], max_length: int, suppress_tokens=None,
                  begin_suppress_tokens=None, use_cache: bool = True, use_graph: bool = True, num_beams: int = 1,
                  length_penalty: float = 1.0, early_stopping: bool = False, return_trace: bool = False,
-                 _beam_path: bool = False) -> list[list[int]]:
+                 _beam_path: bool = False, return_timestamps: bool = False, timestamp_begin: int | None = None,
+                 max_initial_timestamp_index: int | None = None) -> list[list[int]]:
         """Greedy decoding with a forced prefix (<|sot|><|da|><|transcribe|><|notimestamps|> in CoRal's
         evaluation): masked argmax on the GPU (ca_argmax_masked), stop at EOS / max_length.
         num_beams = k >= 2: beam search (`_generate_beam`; length_penalty, early_stopping True / False as in
         transformers); return_trace=True then returns (ids, trace).  num_beams = 1 is the greedy code, untouched
-        (_beam_path=True routes it through the beam launches instead: a test switch)."""
+        (_beam_path=True routes it through the beam launches instead: a test switch).
+        return_timestamps=True: greedy decoding under WhisperTimeStampLogitsProcessor's rules (ca_argmax_timestamps; the
+        prefix then has no <|notimestamps|>, `timestamp_begin` is that token's id + 1, `max_initial_timestamp_index` the
+        generation config's or None).  Not with beams; the one-launch-per-token kernel is bypassed."""
         s, dev = self.s, self.device
         beam = num_beams != 1 or _beam_path
+        ts = None
+        if return_timestamps:
+            if beam:
+                raise ValueError(f"generate(num_beams={num_beams}): return_timestamps=True is not implemented with beam search")
+            if timestamp_begin is None or not 0 <= s.eos_token_id < timestamp_begin <= s.vocab_size:
+                raise ValueError(f"return_timestamps=True needs timestamp_begin (<|notimestamps|> + 1) with eos_token_id < "
+                                 f"timestamp_begin <= vocab_size, got {timestamp_begin!r}")
+            if max_initial_timestamp_index is not None and max_initial_timestamp_index < 0:
+                raise ValueError(f"max_initial_timestamp_index must be None or >= 0, got {max_initial_timestamp_index}")
+            if max_length > s.max_target_positions:
+                raise ValueError(f"max_length {max_length} exceeds the {s.max_target_positions} target positions")
+            ts = (len(prefix), int(timestamp_begin), max_initial_timestamp_index)
         if beam:
             check_beam_arguments(int(input_features.shape[0]), num_beams, length_penalty, early_stopping, {})
             if max_length <= len(prefix) or max_length > s.max_target_positions:
@@ -717,7 +744,7 @@ class WhisperEngine:
             return self._generate_beam(kv, prefix, max_length, sup, sup_begin, num_beams, float(length_penalty),
                                        bool(early_stopping), return_trace, use_graph)
         if use_cache and use_graph and max_length > len(prefix) + 2:
-            return self._generate_graph(kv, prefix, max_length, sup, sup_begin)
+            return self._generate_graph(kv, prefix, max_length, sup, sup_begin, ts)
         ids = torch.tensor([prefix] * B, dtype=torch.int64, device=dev)
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         nxt = torch.empty(B, dtype=torch.int32, device=dev)
@@ -729,24 +756,33 @@ class WhisperEngine:
             else:
                 base = self.decode(ids, enc, kv, last_only=True)[:, 0, :].contiguous()
             mask = sup_begin if ids.shape[1] == len(prefix) else sup
-            ops.argmax_masked(base, mask, nxt, B, V, V)
+            if ts is None:
+                ops.argmax_masked(base, mask, nxt, B, V, V)
+            else:
+                pos = torch.full((B,), ids.shape[1] - 1, dtype=torch.int32, device=dev)
+                ops.argmax_timestamps(base, mask, nxt, B, V, V, ids, pos, ts[0], ts[1], s.eos_token_id, ts[2])
             step = torch.where(done, torch.full_like(nxt, s.pad_token_id), nxt).to(torch.int64)
             ids = torch.cat([ids, step[:, None]], 1)
             feed = step[:, None]
             done |= step == s.eos_token_id
         return ids.tolist()
 
-    def _generate_graph(self, kv, prefix, max_length, sup, sup_begin):
+    def _generate_graph(self, kv, prefix, max_length, sup, sup_begin, ts=None):
         """Greedy loop with the per-token step captured once in a HIP graph and replayed: the ~350 small
         launches of a token (24-32 layers x 14 kernels) cost one graph launch instead of 350 host calls."""
         s, dev = self.s, self.device
         B, V, P = kv[0].shape[0] // (s.max_source_positions * 2 * s.d_model), s.vocab_size, len(prefix)
         cache = self.new_decode_cache(B, max_length)
         g = self._graph_state(cache, kv, s.pad_token_id, s.eos_token_id)
+        g["ts"] = ts  # (begin_index, timestamp_begin, max_initial_timestamp_index) or None
         # the forced prefix and the first free token run eagerly (different shapes / begin-suppress mask)
         ids0 = torch.tensor([prefix] * B, dtype=torch.int64, device=dev)
         base = self.decode_step(ids0, kv, cache).contiguous()
-        ops.argmax_masked(base, sup_begin, g["nxt"], B, V, V)
+        if ts is None:
+            ops.argmax_masked(base, sup_begin, g["nxt"], B, V, V)
+        else:  # (an empty history: only the prefix length matters)
+            ops.argmax_timestamps(base, sup_begin, g["nxt"], B, V, V, ids0, torch.full((B,), P - 1, dtype=torch.int32, device=dev),
+                                  ts[0], ts[1], s.eos_token_id, ts[2])
         g["out"][:, :P] = ids0
         g["out"][:, P] = g["nxt"].long()
         g["done"] |= g["nxt"] == s.eos_token_id
@@ -813,7 +849,7 @@ class WhisperEngine:
                 warnings.warn("coral_amd: " + msg + "; decoding this batch again as a launch sequence and keeping that "
                               "path for this engine (CA_DECODE_STRICT=1 raises instead)")
                 self._persistent_off = True
-                return self._generate_graph(kv, prefix, max_length, sup, sup_begin)
+                return self._generate_graph(kv, prefix, max_length, sup, sup_begin, ts)
         # trim like the eager loop: stop at the first column where every row had already finished
         fin = (out == s.eos_token_id).cumsum(1) > 0
         allfin = fin.all(0)

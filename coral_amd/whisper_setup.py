@@ -19,7 +19,7 @@ from .model_setup import ModelSetup, PreTrainedModelData, _training_args
 from .coral_trainer import CoralTrainer
 from . import specaugment
 from .autograd import attach_backward
-from .whisper import CORAL_WHISPER_SHAPES, N_SAMPLES, WhisperEngine, WhisperShape, sinusoid_positions
+from .whisper import CORAL_WHISPER_SHAPES, HOP, N_SAMPLES, WhisperEngine, WhisperShape, sinusoid_positions
 from .whisper_train import WhisperTrainEngine
 
 logger = logging.getLogger(__package__)
@@ -32,6 +32,10 @@ HUB_SHAPES = {"openai/whisper-tiny": "whisper-xxsmall", "openai/whisper-base": "
 # (language="danish", task="transcribe": R/src/coral/evaluate.py:59, R/src/coral/whisper.py:51-55)
 DANISH_TRANSCRIBE_PREFIX = [50258, 50285, 50359, 50363]
 DANISH_TRANSCRIBE_PREFIX_V3 = [50258, 50285, 50360, 50364]  # large-v3 vocabulary (51866 entries)
+
+
+# generation_config.json of the openai/whisper-* checkpoints
+HUB_MAX_INITIAL_TIMESTAMP_INDEX = 50
 
 
 def prefix_ids(shape: WhisperShape):
@@ -55,6 +59,20 @@ class WhisperFeatureExtractorGPU:
             a = np.asarray(a, dtype=np.float32)[:N_SAMPLES]
             batch[i, : len(a)] = a
         return self.engine.log_mel(torch.from_numpy(batch))
+
+    def whole(self, audio) -> torch.Tensor:
+        """One recording of any length -> log-mel [mels, frames] on the GPU, not cut to 30 s: what the transformers
+        extractor gives with truncation=False (the clamp max(x, max - 8) takes the recording's maximum, not a window's).
+        ca_logmel takes any whole number of hops (frames = N / 160, reflect padding at the true ends, one maximum per
+        row).  Deviation for a length that is no multiple of 160: the trailing part-hop (< 10 ms) is cut BEFORE the
+        transform.  The frame count is the extractor's (len // 160), but the extractor reflect-pads at the true last
+        sample, so the last two frames (whose 400-sample windows reach past the cut) differ slightly from its values;
+        for whole-hop lengths (every pinned fixture) the two agree to the log-mel tolerance."""
+        a = np.asarray(audio, dtype=np.float32)
+        n = max(len(a) // HOP, 3) * HOP
+        buf = np.zeros(n, dtype=np.float32)
+        buf[:min(n, len(a))] = a[:n]
+        return self.engine.log_mel(torch.from_numpy(buf[None]))[0]
 
 
 class WhisperProcessor:
@@ -97,6 +115,9 @@ class WhisperForConditionalGeneration:
         self.spec = spec or dict(apply_spec_augment=False, mask_time_prob=0.0, mask_time_length=10,
                                  mask_feature_prob=0.0, mask_feature_length=64)
         self.layerdrop = layerdrop
+        # what `generate` reads of a checkpoint's generation_config.json: no_timestamps_token_id, lang_to_id, task_to_id,
+        # max_initial_timestamp_index (absent keys: the multilingual vocabulary's ids, no cap - as transformers)
+        self.generation_config: dict = {}
         self.training = False
         self.engine.training = False
         self._rng = np.random
@@ -129,10 +150,14 @@ class WhisperForConditionalGeneration:
             sd = {(k if k.startswith("model.") else "model." + k): v for k, v in sd.items() if k != "proj_out.weight"}
             model.engine.load_state_dict(sd)
             model.engine.refresh_derived()
+            if (path / "generation_config.json").exists():
+                model.generation_config = json.loads((path / "generation_config.json").read_text())
             return model
         if name_or_path not in HUB_SHAPES:
             raise ValueError(f"unknown model {name_or_path!r}")
         model = cls(WhisperShape(**CORAL_WHISPER_SHAPES[HUB_SHAPES[name_or_path]]), device, **kw)
+        model.generation_config = dict(no_timestamps_token_id=prefix_ids(model.shape)[-1],
+                                       max_initial_timestamp_index=HUB_MAX_INITIAL_TIMESTAMP_INDEX)
         logger.warning("no network / hub cache here: %s is instantiated with seeded random weights", name_or_path)
         g = torch.Generator(device=model.engine.device).manual_seed(seed)
         for n in model.engine.exported_names():
@@ -156,6 +181,8 @@ class WhisperForConditionalGeneration:
         model_dir.mkdir(parents=True, exist_ok=True)
         cfg = dict(architectures=["WhisperForConditionalGeneration"], model_type="whisper", **self.shape.__dict__)
         (model_dir / "config.json").write_text(json.dumps(cfg, indent=2))
+        if self.generation_config:
+            (model_dir / "generation_config.json").write_text(json.dumps(self.generation_config, indent=2))
         save_file({k: v.cpu().contiguous() for k, v in self.engine.state_dict().items()},
                   str(model_dir / "model.safetensors"), metadata={"format": "pt"})
 
@@ -192,15 +219,35 @@ class WhisperForConditionalGeneration:
     def backward(self, **kw):
         return self.engine.backward(**kw)
 
+    def forced_prefix(self, return_timestamps: bool = False) -> list[int]:
+        """<|sot|><|da|><|transcribe|><|notimestamps|> from the checkpoint's generation config where it names the ids
+        (lang_to_id, task_to_id, no_timestamps_token_id: `_retrieve_init_tokens`), else the multilingual vocabulary's;
+        return_timestamps=True drops <|notimestamps|>."""
+        gc = self.generation_config
+        prefix = list(prefix_ids(self.shape))
+        if "lang_to_id" in gc and "task_to_id" in gc and "no_timestamps_token_id" in gc:
+            prefix = [self.shape.decoder_start_token_id, int(gc["lang_to_id"]["<|da|>"]), int(gc["task_to_id"]["transcribe"]),
+                      int(gc["no_timestamps_token_id"])]
+        return prefix[:-1] if return_timestamps else prefix
+
     def generate(self, input_features, language="danish", task="transcribe", max_length: int = 225, num_beams: int | None = 1,
-                 length_penalty: float = 1.0, early_stopping=False, **other):
+                 length_penalty: float = 1.0, early_stopping=False, return_timestamps: bool | None = False, **other):
         """Greedy (num_beams 1 / None: other keyword arguments are ignored, as before) or beam search (num_beams >= 2,
-        transformers' semantics; every generation argument this build does not implement is then refused by name)."""
+        transformers' semantics; every generation argument this build does not implement is then refused by name).
+        return_timestamps=True (greedy only): the prefix drops <|notimestamps|> and every pick obeys Whisper's timestamp
+        rules (timestamp_begin = that id + 1, max_initial_timestamp_index from the generation config)."""
         if language not in ("danish", "da") or task != "transcribe":
             raise ValueError("only language='danish', task='transcribe' (CoRal's evaluation call) is wired up")
-        prefix = prefix_ids(self.shape)
+        prefix = self.forced_prefix()
         num_beams = 1 if num_beams is None else num_beams
         kw = {}
+        if return_timestamps:
+            if num_beams != 1:
+                other = dict(other, return_timestamps=return_timestamps)  # refused by name below
+            else:
+                no_ts, prefix = prefix[-1], prefix[:-1]
+                kw = dict(return_timestamps=True, timestamp_begin=no_ts + 1,
+                          max_initial_timestamp_index=self.generation_config.get("max_initial_timestamp_index", None))
         if num_beams != 1:
             from .whisper import check_beam_arguments
 

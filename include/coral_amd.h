@@ -688,7 +688,8 @@ int ca_background_update_fits(int32_t* regs);
  * Whisper log-mel front end.  $TF/models/whisper/feature_extraction_whisper.py:135-168
  * (torch.stft n_fft 400 hop 160 hann, reflect pad, |.|^2 of frames[:-1], mel, log10 clamp
  * 1e-10, max-8 floor, (x+4)/4) ← R/src/coral/whisper.py:51-55, R/src/coral/data.py:747.
- * wave fp32 [B,N] (already padded/truncated to N = 480000), mel_filters fp32 [201,n_mels],
+ * wave fp32 [B,N], N any multiple of 160 from 400 up (480000 = a clip padded / truncated to 30 s; a longer N = a whole
+ * recording, truncation=False: the max-8 floor then uses the recording's maximum), mel_filters fp32 [201,n_mels],
  * out fp32 [B,n_mels,frames], frames = N/160.  ws: ca_logmel_workspace_bytes(B).
  * ---------------------------------------------------------------------------------- */
 int64_t ca_logmel_workspace_bytes(int32_t B);
@@ -713,6 +714,24 @@ int ca_argmax_masked(const float* logits, const uint8_t* suppress, int32_t* out,
 int ca_argmax_advance(const float* logits, const uint8_t* suppress, int32_t* out, int64_t rows, int32_t V, int64_t ldv,
                       uint8_t* done, int64_t* ids, int64_t ld_ids, int32_t* tok, int32_t* pos, int32_t* klen,
                       int32_t pad_id, int32_t eos_id, void* stream);
+/* The greedy pick of generate(return_timestamps=True): WhisperTimeStampLogitsProcessor
+ * ($TF/generation/logits_process.py) on top of the suppress mask, then the first maximum, in one launch.  The row's
+ * history is ids[r, begin_index : pos[r] + 1] (int64 [rows, ld_ids]; pos int32 [rows], the position of the last token);
+ * with last / penultimate = "that token of the history is >= timestamp_begin" (penultimate also true when the history
+ * has fewer than two tokens) and t = the last timestamp of the history, the launch masks, per row:
+ *   timestamp_begin - 1 (<|notimestamps|>);  [timestamp_begin, V) if last and penultimate;  [0, eos_id) if last and not
+ *   penultimate;  [timestamp_begin, t) if last and not penultimate, else [timestamp_begin, t + 1);  for an empty history
+ *   [0, timestamp_begin) and, with max_initial_timestamp_index >= 0, (timestamp_begin + max_initial_timestamp_index, V);
+ *   and all of [0, timestamp_begin) if logsumexp over the unmasked timestamps > max over the unmasked text tokens.
+ * out[r] = the first maximum of what is left (0 if nothing is).  Needs 0 <= eos_id < timestamp_begin <= V. */
+int ca_argmax_timestamps(const float* logits, const uint8_t* suppress, int32_t* out, int64_t rows, int32_t V, int64_t ldv,
+                         const int64_t* ids, int64_t ld_ids, const int32_t* pos, int32_t begin_index,
+                         int32_t timestamp_begin, int32_t eos_id, int32_t max_initial_timestamp_index, void* stream);
+/* The same pick with the bookkeeping of ca_argmax_advance; `ids` / `pos` are both the history read and the state moved. */
+int ca_argmax_timestamps_advance(const float* logits, const uint8_t* suppress, int32_t* out, int64_t rows, int32_t V,
+                                 int64_t ldv, uint8_t* done, int64_t* ids, int64_t ld_ids, int32_t* tok, int32_t* pos,
+                                 int32_t* klen, int32_t pad_id, int32_t eos_id, int32_t begin_index,
+                                 int32_t timestamp_begin, int32_t max_initial_timestamp_index, void* stream);
 /* embedding gather: y[r,:] = table[ids[r],:] + pos[pos_ids[r],:]  (bf16 tables)
  * $TF/models/whisper/modeling_whisper.py:204-212,676. */
 int ca_embed_tokens(const void* table, const void* pos, const int32_t* ids,

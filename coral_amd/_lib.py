@@ -162,6 +162,14 @@ class CaBeamDesc(C.Structure):
 
 
 BEAM_MAX_BEAMS, BEAM_MAX_ROWS = 16, 128  # CA_BEAM_MAX_BEAMS, CA_BEAM_MAX_ROWS
+ALIGN_MAX_TOKENS, ALIGN_MAX_FRAMES, ALIGN_MAX_HEADS, ALIGN_MAX_HEAD_DIM, ALIGN_MAX_FILTER_WIDTH = 447, 1500, 32, 128, 31  # CA_ALIGN_*
+
+
+def align_ws_bytes_per_clip(A, Lw, Fmax):
+    """CA_ALIGN_WS_BYTES_PER_CLIP of include/coral_amd.h."""
+    return A * Fmax * (Lw + 4) * 4
+
+
 FP8_GROUP_MAX = 8  # CA_FP8_GROUP_MAX
 CTC_COLLAPSE_TILE = 4096  # CA_CTC_COLLAPSE_TILE
 KMAJOR, MNMAJOR = 0, 1
@@ -294,6 +302,9 @@ SIGNATURES = {
     "ca_argmax_timestamps": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ca_argmax_timestamps_advance": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32,
                                                _i32, _i32, _i32, _vp]),
+    "ca_whisper_align_cost": (C.c_int, [_vp, C.POINTER(_vp), _i32, C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, _i32, _i64,
+                                        _i64, _vp, _i32, _f32, _i32, _vp, _vp, _i64, _vp]),
+    "ca_dtw_token_times": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ca_embed_tokens": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
     "ca_embed_tokens_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp]),
     "ca_comm_unique_id": (C.c_int, [_vp]),

@@ -80,7 +80,9 @@ def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max
     (coral_amd/longform_whisper.py: windows of 30 s decoded with timestamps, each starting where the last closed
     segment of the one before ended) and its segments are stitched to one text; its id row is the segments' ids in
     order, timestamps included.  return_timestamps=True: every clip takes that loop and the first result is a list of
-    {"text", "chunks": [{"text", "timestamp": (start_s, end_s)}]}.  Both are greedy only."""
+    {"text", "chunks": [{"text", "timestamp": (start_s, end_s)}]}.  return_timestamps="word": the same loop with token
+    timestamps (cross-attention alignment + dynamic time warping, each window with num_frames = min(3000, frames left));
+    one chunk per word (coral_amd/whisper_align.py).  All of these are greedy only."""
     model.eval()
     texts, rows = [], []
     max_length = int(max_length or model.shape.max_target_positions)
@@ -89,8 +91,9 @@ def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max
         raise ValueError(f"num_beams must be a positive integer, got {num_beams}")
     from .whisper import N_SAMPLES
 
-    if return_timestamps not in (True, False, None):
-        raise ValueError(f"return_timestamps must be true or false for a Whisper model, got {return_timestamps!r}")
+    word = isinstance(return_timestamps, str) and return_timestamps == "word"
+    if not word and not any(return_timestamps is v for v in (True, False, None)):
+        raise ValueError(f"return_timestamps must be true, false or \"word\" for a Whisper model, got {return_timestamps!r}")
     looped = [i for i, a in enumerate(arrays) if return_timestamps or len(a) > N_SAMPLES]
     if looped and num_beams > 1:
         raise ValueError(f"num_beams={num_beams}: return_timestamps / recordings longer than 30 s are decoded greedily "
@@ -114,7 +117,7 @@ def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max
     for i, t, r in zip(plain, texts, rows):
         results[i], all_rows[i] = t, r
     timed, timed_rows = _transcribe_whisper_windows(model, processor, [arrays[i] for i in looped], batch_size, max_length,
-                                                    bool(return_timestamps))
+                                                    "word" if word else bool(return_timestamps))
     for i, t, r in zip(looped, timed, timed_rows):
         results[i], all_rows[i] = t, r
     return results, all_rows
@@ -122,35 +125,59 @@ def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max
 
 def _transcribe_whisper_windows(model, processor, arrays, batch_size, max_length, return_timestamps):
     """The long-form loop over `arrays` (clips above 30 s, or every clip when timestamps are asked for), all of them
-    sharing its rounds.  -> (texts, or {"text", "chunks"} per clip with return_timestamps; id rows)."""
+    sharing its rounds.  -> (texts, or {"text", "chunks"} per clip with return_timestamps; id rows).
+    return_timestamps="word": one chunk per word from the windows' token times."""
     from .longform_whisper import run_longform, stitched_ids
     from .whisper import N_SAMPLES
+    from .whisper_align import cap_token_times, offline_decode, word_chunks
+
+    word = return_timestamps == "word"
 
     fe = processor.feature_extractor
     prefix_len, tb = len(model.forced_prefix(return_timestamps=True)), model.forced_prefix()[-1] + 1
     # a clip of at most 30 s is padded to 30 s before the log-mel, as the pipeline's extractor pads it; a longer one
     # keeps its length (truncation=False) and its own maximum
     mels = [fe(a, sampling_rate=fe.sampling_rate)[0] if len(a) <= N_SAMPLES else fe.whole(a) for a in arrays]
+    # the frames that hold audio: what the extractor's attention mask counts.  The seek loop runs over the padded 30 s, as
+    # transformers' does for a clip of one window; the DTW of a window sees only what is left of the true frames
+    true_frames = [min(m.shape[1], max(1, len(a) // 160)) for m, a in zip(mels, arrays)]
 
     def window_generate(batch):
         feats = torch.stack([torch.nn.functional.pad(mels[c][:, seek:seek + 3000], (0, max(0, 3000 - (mels[c].shape[1] - seek))))
                              for c, seek in batch])
+        if word:  # (num_frames = min(3000, true frames left): the padding behind them never enters the DTW)
+            return model.generate(feats, language="danish", task="transcribe", max_length=max_length, return_timestamps=True,
+                                  return_token_timestamps=True,
+                                  num_frames=[min(3000, true_frames[c] - seek) for c, seek in batch])
         return model.generate(feats, language="danish", task="transcribe", max_length=max_length, return_timestamps=True)
 
     s = model.shape
     done = run_longform(window_generate, [m.shape[1] for m in mels], tb, prefix_len, s.pad_token_id, s.eos_token_id,
-                        batch_size=batch_size)
+                        batch_size=batch_size, return_token_timestamps=word)
+    tok = getattr(processor, "tokenizer", None)
+    decode = offline_decode if tok is None else (lambda ids: tok.decode([int(t) for t in ids], skip_special_tokens=False))
     results, rows = [], []
-    for res in done:
-        rows.append([t for _, _, ids in res["segments"] for t in ids])
+    for n, res in enumerate(done):
+        rows.append([t for seg in res["segments"] for t in seg[2]])
         text = processor.batch_decode([stitched_ids(res["segments"], tb)], skip_special_tokens=True)[0]
-        if return_timestamps:
+        if word:
+            # (a window the seek loop opens in the padding behind a short clip's end has no true frame left: F_b = 1,
+            # all its times are its offset; they are capped at the clip's end)
+            times = cap_token_times([t for seg in res["segments"] for t in seg[3]], true_frames[n] * 0.01)
+            chunks = word_chunks(decode, rows[-1], times, tb, s.eos_token_id)
+            results.append(dict(text=text, chunks=chunks))
+        elif return_timestamps:
             chunks = [dict(text=processor.batch_decode([[t for t in ids if t < tb]], skip_special_tokens=True)[0],
-                           timestamp=(start, end)) for start, end, ids in res["segments"]]
+                           timestamp=(start, end)) for start, end, ids, *_ in res["segments"]]
             results.append(dict(text=text, chunks=chunks))
         else:
             results.append(text)
     return results, rows
+
+
+def _whisper_timestamp_mode(value):
+    """`return_timestamps` of evaluation.yaml for a Whisper model: "word" stays, anything else as before (its truth value)."""
+    return "word" if isinstance(value, str) and value == "word" else bool(value or False)
 
 
 def saved_model_type(model_dir) -> str:
@@ -200,7 +227,7 @@ def evaluate(config, examples: list | None = None) -> dict:
                 examples.append(dict(audio=w / np.abs(w).max(), text=""))
         preds, id_rows = transcribe_whisper(model, processor, [e["audio"] for e in examples], config.batch_size,
                                             config.get("generation_max_length", None), config.get("num_beams", 1) or 1,
-                                            return_timestamps=bool(config.get("return_timestamps", False) or False))
+                                            return_timestamps=_whisper_timestamp_mode(config.get("return_timestamps", False)))
         if preds and isinstance(preds[0], dict):
             timed, preds = preds, [p["text"] for p in preds]
     else:

@@ -24,7 +24,7 @@ WINDOW_FRAMES = 3000
 # arguments of transformers' long-form generate that change what the loop does and that this build does not implement
 _LONGFORM_REFUSED = {"temperature": (None, 0.0, 1.0), "condition_on_prev_tokens": (None, False),
                      "no_speech_threshold": (None,), "logprob_threshold": (None,), "compression_ratio_threshold": (None,),
-                     "prompt_ids": (None,), "prompt_condition_type": (None,), "return_token_timestamps": (None, False),
+                     "prompt_ids": (None,), "prompt_condition_type": (None,),
                      "num_beams": (None, 1)}
 
 
@@ -52,10 +52,18 @@ def strip_generated(row, prefix_len: int, pad_id: int, eos_id: int) -> list[int]
 
 
 def segments_of(ids, timestamp_begin: int, time_precision: float = TIME_PRECISION, num_frames: int = WINDOW_FRAMES,
-                time_offset: float = 0.0, return_advance: bool = False):
+                time_offset: float = 0.0, return_advance: bool = False, token_times=None):
     """ids: the tokens one window generated (no prefix, no EOS).  -> [(start_s, end_s, token ids)] as `_retrieve_segment`
-    cuts them (a segment's ids keep its timestamp tokens); return_advance=True: (segments, frames to advance by)."""
+    cuts them (a segment's ids keep its timestamp tokens); return_advance=True: (segments, frames to advance by).
+    token_times: the window's time per token of `ids` (float32, from 0 at the window's start): a segment is then
+    (start_s, end_s, token ids, token times), the times cut like the ids and shifted by the offset in float32, as
+    `_retrieve_segment` adds its float64 scalar to the float32 tensor."""
     ids = [int(t) for t in ids]
+    if token_times is not None:
+        token_times = np.asarray(token_times, dtype=np.float32)
+        if token_times.shape != (len(ids),):
+            raise ValueError(f"segments_of: {token_times.shape} token times for {len(ids)} tokens")
+    timed = (lambda a, b: (token_times[a:b] + np.float32(time_offset),)) if token_times is not None else (lambda a, b: ())
     is_ts = [t >= timestamp_begin for t in ids]
     single_ending = is_ts[-2:] == [False, True]
     slices = [i + 1 for i in range(len(ids) - 1) if is_ts[i] and is_ts[i + 1]]
@@ -71,7 +79,8 @@ def segments_of(ids, timestamp_begin: int, time_precision: float = TIME_PRECISIO
             is_last = i == len(slices) - 1
             start = tokens[0] - timestamp_begin
             end = tokens[-1 if (not is_last or single_ending) else -2] - timestamp_begin
-            segments.append((time_offset + float(start) * time_precision, time_offset + float(end) * time_precision, tokens))
+            segments.append((time_offset + float(start) * time_precision, time_offset + float(end) * time_precision, tokens)
+                            + timed(last, cur))
             last = cur
         if single_ending:
             advance = num_frames  # no speech after the last timestamp
@@ -83,16 +92,19 @@ def segments_of(ids, timestamp_begin: int, time_precision: float = TIME_PRECISIO
         last_pos = int(np.float32(num_frames) * np.float32(TIME_PRECISION_FEATURES) / np.float32(time_precision))
         if stamps and stamps[-1] != timestamp_begin:
             last_pos = float(stamps[-1] - timestamp_begin)
-        segments.append((time_offset, time_offset + last_pos * time_precision, ids))
+        segments.append((time_offset, time_offset + last_pos * time_precision, ids) + timed(0, len(ids)))
         advance = num_frames
     return (segments, int(advance)) if return_advance else segments
 
 
 def run_longform(window_generate, num_frames, timestamp_begin: int, prefix_len: int, pad_id: int, eos_id: int,
-                 time_precision: float = TIME_PRECISION, batch_size: int | None = None, **other):
+                 time_precision: float = TIME_PRECISION, batch_size: int | None = None,
+                 return_token_timestamps: bool | None = False, **other):
     """window_generate([(clip, seek), ...]) -> one generated id row per entry (prefix included, padded as `generate`
     pads).  num_frames: log-mel frames per clip.  -> per clip dict(segments=[(start_s, end_s, ids)], windows=[(seek,
-    generated ids)]).  batch_size: at most that many windows per call (None: all unfinished clips at once)."""
+    generated ids)]).  batch_size: at most that many windows per call (None: all unfinished clips at once).
+    return_token_timestamps=True: window_generate returns (id rows, float32 times [rows, row length]); segments are
+    (start_s, end_s, ids, token times) and windows (seek, generated ids, their times)."""
     check_longform_arguments(other)
     num_frames = [int(n) for n in num_frames]
     seek = [0] * len(num_frames)
@@ -105,21 +117,29 @@ def run_longform(window_generate, num_frames, timestamp_begin: int, prefix_len: 
         for a in range(0, len(todo), step):
             batch = todo[a:a + step]
             rows = window_generate([(i, seek[i]) for i in batch])
+            times = [None] * len(batch)
+            if return_token_timestamps:
+                rows, times = rows
+                if len(times) != len(rows):
+                    raise ValueError(f"window_generate returned {len(times)} rows of token times for {len(rows)} id rows")
             if len(rows) != len(batch):
                 raise ValueError(f"window_generate returned {len(rows)} rows for {len(batch)} windows")
-            for i, row in zip(batch, rows):
+            for i, row, tt in zip(batch, rows, times):
                 gen = strip_generated(row, prefix_len, pad_id, eos_id)
                 frames = min(num_frames[i] - seek[i], WINDOW_FRAMES)
                 offset = seek[i] * time_precision / INPUT_STRIDE
-                out[i]["windows"].append((seek[i], gen))
+                if tt is not None:  # (the generated tokens' share of the row's times)
+                    tt = np.asarray(tt, dtype=np.float32)[prefix_len:prefix_len + len(gen)]
+                out[i]["windows"].append((seek[i], gen) if tt is None else (seek[i], gen, tt))
                 if not gen:  # (cannot happen under the timestamp rules: the first token is a timestamp)
                     seek[i] += frames
                     continue
-                segs, adv = segments_of(gen, timestamp_begin, time_precision, frames, offset, return_advance=True)
+                segs, adv = segments_of(gen, timestamp_begin, time_precision, frames, offset, return_advance=True,
+                                        token_times=tt)
                 out[i]["segments"] += segs
                 seek[i] += adv
 
 
 def stitched_ids(segments, timestamp_begin: int) -> list[int]:
     """The text tokens of a recording's segments in order (timestamps dropped)."""
-    return [t for _, _, ids in segments for t in ids if t < timestamp_begin]
+    return [t for seg in segments for t in seg[2] if t < timestamp_begin]

@@ -754,6 +754,59 @@ def argmax_timestamps_advance(logits, suppress, out, rows, V, ldv, done, ids, to
                                              _stream()), "ca_argmax_timestamps_advance")
 
 
+ALIGN_WS_CAP_BYTES = 64 << 20  # fp32 scratch of ca_whisper_align_cost: clips are grouped to stay below it
+
+
+def whisper_align_cost(q, cross_k, layer_head, B, Lw, Te, H, hd, ldk, skb, frames, Fmax, scale, filter_width,
+                       ws_cap_bytes=None):
+    """-> the DTW cost fp32 [B, Lw, Fmax] of ca_whisper_align_cost.  q bf16 [A, B, Lw, hd]; cross_k: per decoder layer the
+    tensor whose rows start with the encoder keys; layer_head: [(layer, head)]; frames: device int32 [B].  The raw-weight
+    scratch is min(ws_cap_bytes, what B clips need), never below one clip's."""
+    from .whisper_align import check_align_limits
+
+    A = len(layer_head)
+    check_align_limits(A, Lw, Fmax, hd, Te, filter_width)
+    if q.dtype != torch.bfloat16 or not q.is_contiguous() or q.numel() != A * B * Lw * hd:
+        raise CoralAmdError("whisper_align_cost: q must be a contiguous bf16 [A, B, Lw, hd]")
+    if frames.dtype != torch.int32 or frames.numel() != B or any(k.dtype != torch.bfloat16 for k in cross_k):
+        raise CoralAmdError("whisper_align_cost: frames must be int32 [B], the keys bf16")
+    per_clip = _lib.align_ws_bytes_per_clip(A, Lw, Fmax)
+    cap = ALIGN_WS_CAP_BYTES if ws_cap_bytes is None else int(ws_cap_bytes)
+    nbytes = per_clip * max(1, min(B, cap // per_clip))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+    cost = torch.empty(B, Lw, Fmax, dtype=torch.float32, device=q.device)
+    kptr = (C.c_void_p * len(cross_k))(*[_p(k) for k in cross_k])
+    lh = (C.c_int32 * (2 * A))(*[int(v) for pair in layer_head for v in pair])
+    check(lib().ca_whisper_align_cost(_p(q), kptr, len(cross_k), lh, A, B, Lw, Te, H, hd, ldk, skb, _p(frames), Fmax,
+                                      float(scale), int(filter_width), _p(cost), _p(ws), nbytes, _stream()),
+          "ca_whisper_align_cost")
+    return cost
+
+
+def dtw_token_times(cost, frames, return_path=False):
+    """cost fp32 [B, Lw, Fmax], frames device int32 [B] -> jump frames int32 [B, Lw] (ca_dtw_token_times); return_path:
+    (jump, [(text indices, time indices)] per clip, in path order, on the host)."""
+    from .whisper_align import check_align_limits
+
+    B, Lw, Fmax = cost.shape
+    check_align_limits(1, Lw, Fmax, 8)
+    if cost.dtype != torch.float32 or not cost.is_contiguous() or frames.dtype != torch.int32 or frames.numel() != B:
+        raise CoralAmdError("dtw_token_times: cost must be a contiguous fp32 [B, Lw, Fmax], frames int32 [B]")
+    dev = cost.device
+    trace = torch.empty(B, Lw, Fmax, dtype=torch.uint8, device=dev)
+    jump = torch.empty(B, Lw, dtype=torch.int32, device=dev)
+    pt = pj = pn = None
+    if return_path:
+        pt = torch.empty(B, Lw + Fmax, dtype=torch.int32, device=dev)
+        pj, pn = torch.empty_like(pt), torch.empty(B, dtype=torch.int32, device=dev)
+    check(lib().ca_dtw_token_times(_p(cost), B, Lw, _p(frames), Fmax, _p(trace), _p(jump), _p(pt), _p(pj), _p(pn), _stream()),
+          "ca_dtw_token_times")
+    if not return_path:
+        return jump
+    pt, pj, pn = pt.cpu().numpy(), pj.cpu().numpy(), pn.cpu().tolist()
+    return jump, [(pt[b, :n][::-1].copy(), pj[b, :n][::-1].copy()) for b, n in enumerate(pn)]
+
+
 def beam_select_workspace_bytes(B, k, V):
     return lib().ca_beam_select_workspace_bytes(B, k, V)
 

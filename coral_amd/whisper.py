@@ -165,7 +165,7 @@ def sinusoid_positions(length: int, channels: int, max_timescale: float = 10000.
 _BEAM_REFUSED = {"num_return_sequences": (None, 1), "do_sample": (None, False), "temperature": (None, 1.0), "top_k": (None,),
                  "top_p": (None, 1.0), "typical_p": (None, 1.0), "num_beam_groups": (None, 1), "diversity_penalty": (None, 0.0),
                  "repetition_penalty": (None, 1.0), "no_repeat_ngram_size": (None, 0), "penalty_alpha": (None,),
-                 "return_timestamps": (None, False), "low_memory": (None, False), "constraints": (None,),
+                 "return_timestamps": (None, False), "return_token_timestamps": (None, False), "low_memory": (None, False), "constraints": (None,),
                  "force_words_ids": (None,), "bad_words_ids": (None,), "min_length": (None, 0), "min_new_tokens": (None,),
                  "max_new_tokens": (None,), "logits_processor": (None,), "stopping_criteria": (None,),
                  "prefix_allowed_tokens_fn": (None,), "assistant_model": (None,), "no_speech_threshold": (None,),
@@ -698,7 +698,8 @@ class WhisperEngine:
                  begin_suppress_tokens=None, use_cache: bool = True, use_graph: bool = True, num_beams: int = 1,
                  length_penalty: float = 1.0, early_stopping: bool = False, return_trace: bool = False,
                  _beam_path: bool = False, return_timestamps: bool = False, timestamp_begin: int | None = None,
-                 max_initial_timestamp_index: int | None = None) -> list[list[int]]:
+                 max_initial_timestamp_index: int | None = None, return_token_timestamps: bool = False,
+                 alignment_heads=None, num_frames=None, median_filter_width: int = 7):
         """Greedy decoding with a forced prefix (<|sot|><|da|><|transcribe|><|notimestamps|> in CoRal's
         evaluation): masked argmax on the GPU (ca_argmax_masked), stop at EOS / max_length.
         num_beams = k >= 2: beam search (`_generate_beam`; length_penalty, early_stopping True / False as in
@@ -706,10 +707,23 @@ class WhisperEngine:
         (_beam_path=True routes it through the beam launches instead: a test switch).
         return_timestamps=True: greedy decoding under WhisperTimeStampLogitsProcessor's rules (ca_argmax_timestamps; the
         prefix then has no <|notimestamps|>, `timestamp_begin` is that token's id + 1, `max_initial_timestamp_index` the
-        generation config's or None).  Not with beams; the one-launch-per-token kernel is bypassed."""
+        generation config's or None).  Not with beams; the one-launch-per-token kernel is bypassed.
+        return_token_timestamps=True (with return_timestamps=True, greedy only): -> (ids, times), times float32 seconds
+        [B, len(ids[0])] from the cross-attention of `alignment_heads` [(layer, head)] and dynamic time warping
+        (`token_timestamps`); num_frames: valid log-mel frames per clip (None: all)."""
         s, dev = self.s, self.device
         beam = num_beams != 1 or _beam_path
         ts = None
+        if return_token_timestamps:
+            from .whisper_align import check_alignment_heads
+
+            if beam:
+                raise ValueError(f"generate(num_beams={num_beams}): return_token_timestamps=True is not implemented with beam "
+                                 "search")
+            if not return_timestamps:
+                raise ValueError("return_token_timestamps=True needs return_timestamps=True (the word mode of the ASR pipeline "
+                                 "sets both)")
+            alignment_heads = check_alignment_heads(alignment_heads, s.decoder_layers, s.decoder_attention_heads)
         if return_timestamps:
             if beam:
                 raise ValueError(f"generate(num_beams={num_beams}): return_timestamps=True is not implemented with beam search")
@@ -744,7 +758,10 @@ class WhisperEngine:
             return self._generate_beam(kv, prefix, max_length, sup, sup_begin, num_beams, float(length_penalty),
                                        bool(early_stopping), return_trace, use_graph)
         if use_cache and use_graph and max_length > len(prefix) + 2:
-            return self._generate_graph(kv, prefix, max_length, sup, sup_begin, ts)
+            rows = self._generate_graph(kv, prefix, max_length, sup, sup_begin, ts)
+            if return_token_timestamps:
+                return rows, self.token_timestamps(rows, kv, len(prefix), alignment_heads, num_frames, median_filter_width)
+            return rows
         ids = torch.tensor([prefix] * B, dtype=torch.int64, device=dev)
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         nxt = torch.empty(B, dtype=torch.int32, device=dev)
@@ -765,7 +782,73 @@ class WhisperEngine:
             ids = torch.cat([ids, step[:, None]], 1)
             feed = step[:, None]
             done |= step == s.eos_token_id
+        if return_token_timestamps:
+            rows = ids.tolist()
+            return rows, self.token_timestamps(rows, kv, len(prefix), alignment_heads, num_frames, median_filter_width)
         return ids.tolist()
+
+    # ---- token timestamps (cross-attention alignment + DTW) ------------------------------------------------------------
+    def alignment_queries(self, ids, kv: list, heads: list, prefix_len: int) -> torch.Tensor:
+        """One teacher-forced decoder pass over ids [B, L] with `decode`'s launch sequence, up to the last alignment
+        layer's cross-attention: -> bf16 [A, B, L - prefix_len, head_dim], the queries of the alignment heads at the
+        positions that consume tokens prefix_len .. L-1 (w["ca"]["q"] after CrossAttnBlock.forward of their layer)."""
+        self._await_all()
+        s, dev = self.s, self.device
+        ids = torch.as_tensor(ids)
+        B, L = ids.shape
+        d, H, Te = s.d_model, s.decoder_attention_heads, s.max_source_positions
+        hd, M = d // H, B * L
+        # L changes from batch to batch: a workspace made for this pass is not kept (`_dec_ws` never evicts)
+        fresh = (B, L) not in self._dec_ws
+        w = self._decoder_ws(B, L)
+        if fresh:
+            del self._dec_ws[(B, L)]
+        flat = ids.to(dev, torch.int32).contiguous().view(-1)
+        pos = torch.arange(L, dtype=torch.int32, device=dev).repeat(B)
+        h0, h1 = w["h"]
+        self._embed(flat, pos, h0, M)
+        q = torch.empty(len(heads), B, L - prefix_len, hd, dtype=torch.bfloat16, device=dev)
+        last = max(l for l, _ in heads)
+        for l, (sa, ca, ff) in enumerate(self.dec_blocks):
+            sa.forward(h0, h1, w["sa"], B, L)
+            ca.forward(h1, h0, w["ca"], B, L, Te, kv=kv[l])
+            ql = w["ca"]["q"][:M * d].view(B, L, H, hd)
+            for a, (la, h) in enumerate(heads):
+                if la == l:
+                    q[a].copy_(ql[:, prefix_len:, h, :])
+            if l == last:
+                break
+            ff.forward(h0, h1, w["ff"], M)
+            h0, h1 = h1, h0
+        return q
+
+    def token_timestamps(self, rows, kv: list, prefix_len: int, alignment_heads, num_frames=None,
+                         median_filter_width: int = 7, return_parts: bool = False):
+        """`WhisperGenerationMixin._extract_token_timestamps` for generated id rows [B, Ltot] (prefix included, padded as
+        `generate` pads): the DTW tokens are the input positions prefix_len .. Ltot-2.  -> float32 seconds [B, Ltot];
+        return_parts: (times, dict(cost, jump, frames)) with the device tensors of the two kernels."""
+        from .whisper_align import check_align_limits, check_alignment_heads, frames_of, times_from_jumps
+
+        s, dev = self.s, self.device
+        d, H, Te = s.d_model, s.decoder_attention_heads, s.max_source_positions
+        hd = d // H
+        heads = check_alignment_heads(alignment_heads, s.decoder_layers, H)
+        ids = torch.as_tensor(rows)
+        B, Ltot = ids.shape
+        Lw = Ltot - 1 - prefix_len
+        frames = frames_of(num_frames, B, Te)
+        Fmax = max(frames)
+        check_align_limits(len(heads), Lw, Fmax, hd, Te, median_filter_width)
+        if Lw <= 0:
+            times = times_from_jumps(np.zeros((B, 0), dtype=np.int32), prefix_len, Ltot)
+            return (times, dict(cost=None, jump=None, frames=frames)) if return_parts else times
+        q = self.alignment_queries(ids[:, :Ltot - 1], kv, heads, prefix_len)
+        fdev = torch.tensor(frames, dtype=torch.int32).to(dev)
+        cost = ops.whisper_align_cost(q, kv, heads, B, Lw, Te, H, hd, 2 * d, Te * 2 * d, fdev, Fmax, hd ** -0.5,
+                                      median_filter_width)
+        jump = ops.dtw_token_times(cost, fdev)
+        times = times_from_jumps(jump.cpu().numpy(), prefix_len, Ltot)
+        return (times, dict(cost=cost, jump=jump, frames=frames)) if return_parts else times
 
     def _generate_graph(self, kv, prefix, max_length, sup, sup_begin, ts=None):
         """Greedy loop with the per-token step captured once in a HIP graph and replayed: the ~350 small

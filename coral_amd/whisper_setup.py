@@ -118,6 +118,7 @@ class WhisperForConditionalGeneration:
         # what `generate` reads of a checkpoint's generation_config.json: no_timestamps_token_id, lang_to_id, task_to_id,
         # max_initial_timestamp_index (absent keys: the multilingual vocabulary's ids, no cap - as transformers)
         self.generation_config: dict = {}
+        self.median_filter_width = 7  # config.json's `median_filter_width` (token timestamps)
         self.training = False
         self.engine.training = False
         self._rng = np.random
@@ -144,6 +145,7 @@ class WhisperForConditionalGeneration:
             cfg = json.loads((path / "config.json").read_text())
             fields = WhisperShape.__dataclass_fields__
             model = cls(WhisperShape(**{k: cfg[k] for k in fields if k in cfg}), device, **kw)
+            model.median_filter_width = int(cfg.get("median_filter_width", 7))
             from .modeling import load_checkpoint_tensors
 
             sd = load_checkpoint_tensors(path)
@@ -179,7 +181,8 @@ class WhisperForConditionalGeneration:
 
         model_dir = Path(model_dir)
         model_dir.mkdir(parents=True, exist_ok=True)
-        cfg = dict(architectures=["WhisperForConditionalGeneration"], model_type="whisper", **self.shape.__dict__)
+        cfg = dict(architectures=["WhisperForConditionalGeneration"], model_type="whisper", **self.shape.__dict__,
+                   median_filter_width=int(self.median_filter_width))
         (model_dir / "config.json").write_text(json.dumps(cfg, indent=2))
         if self.generation_config:
             (model_dir / "generation_config.json").write_text(json.dumps(self.generation_config, indent=2))
@@ -231,11 +234,15 @@ class WhisperForConditionalGeneration:
         return prefix[:-1] if return_timestamps else prefix
 
     def generate(self, input_features, language="danish", task="transcribe", max_length: int = 225, num_beams: int | None = 1,
-                 length_penalty: float = 1.0, early_stopping=False, return_timestamps: bool | None = False, **other):
+                 length_penalty: float = 1.0, early_stopping=False, return_timestamps: bool | None = False,
+                 return_token_timestamps: bool | None = False, num_frames=None, **other):
         """Greedy (num_beams 1 / None: other keyword arguments are ignored, as before) or beam search (num_beams >= 2,
         transformers' semantics; every generation argument this build does not implement is then refused by name).
         return_timestamps=True (greedy only): the prefix drops <|notimestamps|> and every pick obeys Whisper's timestamp
-        rules (timestamp_begin = that id + 1, max_initial_timestamp_index from the generation config)."""
+        rules (timestamp_begin = that id + 1, max_initial_timestamp_index from the generation config).
+        return_token_timestamps=True (with return_timestamps=True, greedy only): -> (ids, float32 seconds per token) from
+        the cross-attention of the generation config's `alignment_heads` (absent: transformers' error) and dynamic time
+        warping; num_frames: valid log-mel frames per clip; `median_filter_width` is the checkpoint config's (default 7)."""
         if language not in ("danish", "da") or task != "transcribe":
             raise ValueError("only language='danish', task='transcribe' (CoRal's evaluation call) is wired up")
         prefix = self.forced_prefix()
@@ -248,6 +255,16 @@ class WhisperForConditionalGeneration:
                 no_ts, prefix = prefix[-1], prefix[:-1]
                 kw = dict(return_timestamps=True, timestamp_begin=no_ts + 1,
                           max_initial_timestamp_index=self.generation_config.get("max_initial_timestamp_index", None))
+        if return_token_timestamps:
+            from .whisper_align import check_alignment_heads
+
+            if num_beams != 1:
+                other = dict(other, return_token_timestamps=return_token_timestamps)  # refused by name below
+            else:
+                heads = check_alignment_heads(self.generation_config.get("alignment_heads"), self.shape.decoder_layers,
+                                              self.shape.decoder_attention_heads)
+                kw.update(return_token_timestamps=True, alignment_heads=heads, num_frames=num_frames,
+                          median_filter_width=int(self.median_filter_width))
         if num_beams != 1:
             from .whisper import check_beam_arguments
 

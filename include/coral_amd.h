@@ -741,6 +741,41 @@ int ca_embed_tokens_bwd(const void* dy, const int32_t* ids, const int32_t* pos_i
                         float* dpos, int64_t rows, int32_t C, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Whisper word timestamps (csrc/align.hip): the cross-attention alignment cost and dynamic time warping of
+ * `WhisperGenerationMixin._extract_token_timestamps` ($TF/models/whisper/generation_whisper.py).
+ * Beyond the limits below both entries return CA_ERR_UNSUPPORTED. */
+#define CA_ALIGN_MAX_TOKENS 447
+#define CA_ALIGN_MAX_FRAMES 1500
+#define CA_ALIGN_MAX_HEADS 32
+#define CA_ALIGN_MAX_HEAD_DIM 128
+#define CA_ALIGN_MAX_FILTER_WIDTH 31
+/* workspace bytes ca_whisper_align_cost needs per clip it works on at once (fp32 raw weights + fp64 per-frame mean / std) */
+#define CA_ALIGN_WS_BYTES_PER_CLIP(A, Lw, Fmax) ((int64_t)(A) * (Fmax) * ((int64_t)(Lw) + 4) * 4)
+/* cost fp32 [B, Lw, Fmax] (entries at frames >= F_b are written as 0) from
+ *   W[b,a,t,j] = softmax over all Te keys of scale * q[a,b,t,:] . K[b,j,:], cropped to j < F_b = frames[b] (read on the
+ *                device and clamped to [1, Fmax]);
+ *   standardised per (b,a,j) over t (mean, population standard deviation; formed in fp64, rounded to fp32), median-filtered along j with `filter_width`
+ *   taps and reflect padding (skipped when F_b <= filter_width / 2; NaN sorts last, as torch.sort), averaged over a,
+ *   negated.
+ * q: bf16 [A, B, Lw, hd], the queries of the A alignment heads.  cross_k: HOST array of n_layers device pointers, layer
+ * l's encoder keys as bf16 rows of ldk elements, skb elements per clip, head h at column h * hd.  layer_head: HOST int32
+ * [A][2] of (layer, head).  frames: DEVICE int32 [B].  ws: device scratch of ws_bytes; the clips are worked on in groups
+ * of min(B, ws_bytes / CA_ALIGN_WS_BYTES_PER_CLIP) (at least one must fit), three launches per group. */
+int ca_whisper_align_cost(const void* q, const void* const* cross_k, int32_t n_layers, const int32_t* layer_head,
+                          int32_t A, int32_t B, int32_t Lw, int32_t Te, int32_t H, int32_t hd, int64_t ldk, int64_t skb,
+                          const int32_t* frames, int32_t Fmax, float scale, int32_t filter_width, float* cost, void* ws,
+                          int64_t ws_bytes, void* stream);
+/* Dynamic time warping of cost fp32 [B, Lw, Fmax] per clip over its first F_b = frames[b] columns (DEVICE int32 [B],
+ * clamped to [1, Fmax]); one workgroup per clip.  Table (Lw + 1) x (F_b + 1), cost[0,0] = 0, the rest +inf; fp32
+ * cost[i,j] = C[i-1,j-1] + c with c the diagonal if strictly below both others (trace 0), else the upper cell if strictly
+ * below both others (trace 1), else the left cell (trace 2); backtrace from (Lw, F_b) with row 0 read as 2 and column 0
+ * as 1.  jump int32 [B, Lw]: the time index of the first path step of every text index.  trace: uint8 scratch
+ * [B, Lw, Fmax].  path_text / path_time int32 [B, Lw + Fmax] and path_len int32 [B] (all three or none): the path in
+ * backtrace order, i.e. from its END to its start. */
+int ca_dtw_token_times(const float* cost, int32_t B, int32_t Lw, const int32_t* frames, int32_t Fmax, uint8_t* trace,
+                       int32_t* jump, int32_t* path_text, int32_t* path_time, int32_t* path_len, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Greedy decoding: ONE launch per token for a whole Whisper decoder (round 6).
  *
  * Replaces, for a batch of at most 16 clips, the ~170 dependent launches of a decoded token - per layer

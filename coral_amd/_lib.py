@@ -302,6 +302,9 @@ SIGNATURES = {
     "ca_argmax_timestamps": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ca_argmax_timestamps_advance": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32,
                                                _i32, _i32, _i32, _vp]),
+    "ca_pick_scored_advance": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _f32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                                         _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "ca_row_token_prob": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _i32, _vp]),
     "ca_whisper_align_cost": (C.c_int, [_vp, C.POINTER(_vp), _i32, C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, _i32, _i64,
                                         _i64, _vp, _i32, _f32, _i32, _vp, _vp, _i64, _vp]),
     "ca_dtw_token_times": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

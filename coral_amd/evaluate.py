@@ -69,7 +69,8 @@ def transcribe(model, processor, arrays: list, batch_size: int = 16, chunk_lengt
 
 
 def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max_length: int | None = None,
-                       num_beams: int = 1, return_timestamps: bool = False):
+                       num_beams: int = 1, return_timestamps: bool = False, temperature=None, logprob_threshold=None,
+                       compression_ratio_threshold=None, no_speech_threshold=None, sample_seed: int = 0):
     """The Whisper branch of the ASR pipeline ($TF/pipelines/automatic_speech_recognition.py:345,529,600): pad / trim
     every clip to 30 s, log-mel on the GPU, `model.generate(input_features, language="danish", task="transcribe")`
     (R/src/coral/evaluate.py:56-60), decode the generated ids without special tokens.
@@ -82,8 +83,15 @@ def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max
     order, timestamps included.  return_timestamps=True: every clip takes that loop and the first result is a list of
     {"text", "chunks": [{"text", "timestamp": (start_s, end_s)}]}.  return_timestamps="word": the same loop with token
     timestamps (cross-attention alignment + dynamic time warping, each window with num_frames = min(3000, frames left));
-    one chunk per word (coral_amd/whisper_align.py).  All of these are greedy only."""
+    one chunk per word (coral_amd/whisper_align.py).  All of these are greedy only.
+    temperature (a number or a list tried in order), logprob_threshold, compression_ratio_threshold, no_speech_threshold:
+    transformers' temperature fallback (coral_amd/longform_whisper.py `FallbackPolicy`): every clip then takes the window
+    loop; a window that fails a threshold is decoded again with sampling at the next temperature (uniforms from a CPU
+    generator seeded with sample_seed), one that is silence is skipped; with return_timestamps every chunk's window
+    carries avg_logprob, temperature and no_speech_prob under "windows".  Not with beams, not with "word"."""
     model.eval()
+    policy = model.fallback_policy(temperature, logprob_threshold, compression_ratio_threshold, no_speech_threshold,
+                                   sample_seed)
     texts, rows = [], []
     max_length = int(max_length or model.shape.max_target_positions)
     num_beams = int(num_beams or 1)
@@ -94,7 +102,13 @@ def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max
     word = isinstance(return_timestamps, str) and return_timestamps == "word"
     if not word and not any(return_timestamps is v for v in (True, False, None)):
         raise ValueError(f"return_timestamps must be true, false or \"word\" for a Whisper model, got {return_timestamps!r}")
-    looped = [i for i, a in enumerate(arrays) if return_timestamps or len(a) > N_SAMPLES]
+    if policy is not None:
+        if num_beams > 1:
+            raise ValueError(f"num_beams={num_beams}: temperature / logprob_threshold / compression_ratio_threshold / "
+                             "no_speech_threshold are not implemented with beam search")
+        if word:
+            raise ValueError("return_timestamps=\"word\" is not implemented with temperature fallback")
+    looped = [i for i, a in enumerate(arrays) if return_timestamps or policy is not None or len(a) > N_SAMPLES]
     if looped and num_beams > 1:
         raise ValueError(f"num_beams={num_beams}: return_timestamps / recordings longer than 30 s are decoded greedily "
                          "only (beam search with timestamps is not implemented)")
@@ -117,13 +131,13 @@ def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max
     for i, t, r in zip(plain, texts, rows):
         results[i], all_rows[i] = t, r
     timed, timed_rows = _transcribe_whisper_windows(model, processor, [arrays[i] for i in looped], batch_size, max_length,
-                                                    "word" if word else bool(return_timestamps))
+                                                    "word" if word else bool(return_timestamps), policy)
     for i, t, r in zip(looped, timed, timed_rows):
         results[i], all_rows[i] = t, r
     return results, all_rows
 
 
-def _transcribe_whisper_windows(model, processor, arrays, batch_size, max_length, return_timestamps):
+def _transcribe_whisper_windows(model, processor, arrays, batch_size, max_length, return_timestamps, policy=None):
     """The long-form loop over `arrays` (clips above 30 s, or every clip when timestamps are asked for), all of them
     sharing its rounds.  -> (texts, or {"text", "chunks"} per clip with return_timestamps; id rows).
     return_timestamps="word": one chunk per word from the windows' token times."""
@@ -152,8 +166,18 @@ def _transcribe_whisper_windows(model, processor, arrays, batch_size, max_length
         return model.generate(feats, language="danish", task="transcribe", max_length=max_length, return_timestamps=True)
 
     s = model.shape
+    if policy is not None:
+        attempt = model.fallback_attempts(policy, max_length, True)
+
+        def window_generate(batch, temperature, uniforms):  # noqa: F811  (the protocol under a policy)
+            feats = {(c, seek): torch.nn.functional.pad(mels[c][:, seek:seek + 3000],
+                                                        (0, max(0, 3000 - (mels[c].shape[1] - seek)))) for c, seek in batch}
+            return attempt(batch, temperature, uniforms, feats)
+
     done = run_longform(window_generate, [m.shape[1] for m in mels], tb, prefix_len, s.pad_token_id, s.eos_token_id,
-                        batch_size=batch_size, return_token_timestamps=word)
+                        batch_size=batch_size, return_token_timestamps=word, fallback=policy,
+                        vocab_size=s.vocab_size if policy is not None else None,
+                        max_length=max_length if policy is not None else None)
     tok = getattr(processor, "tokenizer", None)
     decode = offline_decode if tok is None else (lambda ids: tok.decode([int(t) for t in ids], skip_special_tokens=False))
     results, rows = [], []
@@ -170,6 +194,8 @@ def _transcribe_whisper_windows(model, processor, arrays, batch_size, max_length
             chunks = [dict(text=processor.batch_decode([[t for t in ids if t < tb]], skip_special_tokens=True)[0],
                            timestamp=(start, end)) for start, end, ids, *_ in res["segments"]]
             results.append(dict(text=text, chunks=chunks))
+            if policy is not None:
+                results[-1]["windows"] = res["window_stats"]
         else:
             results.append(text)
     return results, rows
@@ -178,6 +204,11 @@ def _transcribe_whisper_windows(model, processor, arrays, batch_size, max_length
 def _whisper_timestamp_mode(value):
     """`return_timestamps` of evaluation.yaml for a Whisper model: "word" stays, anything else as before (its truth value)."""
     return "word" if isinstance(value, str) and value == "word" else bool(value or False)
+
+
+def _plain(value):
+    """A temperature from the configuration: a number, None, or a list of numbers as a tuple."""
+    return value if value is None or isinstance(value, (int, float)) else tuple(float(t) for t in value)
 
 
 def saved_model_type(model_dir) -> str:
@@ -227,7 +258,12 @@ def evaluate(config, examples: list | None = None) -> dict:
                 examples.append(dict(audio=w / np.abs(w).max(), text=""))
         preds, id_rows = transcribe_whisper(model, processor, [e["audio"] for e in examples], config.batch_size,
                                             config.get("generation_max_length", None), config.get("num_beams", 1) or 1,
-                                            return_timestamps=_whisper_timestamp_mode(config.get("return_timestamps", False)))
+                                            return_timestamps=_whisper_timestamp_mode(config.get("return_timestamps", False)),
+                                            temperature=_plain(config.get("temperature", None)),
+                                            logprob_threshold=config.get("logprob_threshold", None),
+                                            compression_ratio_threshold=config.get("compression_ratio_threshold", None),
+                                            no_speech_threshold=config.get("no_speech_threshold", None),
+                                            sample_seed=int(config.get("sample_seed", 0) or 0))
         if preds and isinstance(preds[0], dict):
             timed, preds = preds, [p["text"] for p in preds]
     else:

@@ -5,14 +5,21 @@ Restated from the installed transformers ($TF/models/whisper/generation_whisper.
   * `segments_of`  - `_retrieve_segment`: a window's generated ids are cut at every closed timestamp pair; the window
     then advances to the last closed pair, or by all its frames when it ends in a single timestamp or holds no pair;
   * `run_longform` - the loop of `WhisperGenerationMixin.generate` for inputs above 3000 frames with the arguments the
-    ASR pipeline passes (R/src/coral/evaluate.py runs `pipeline(...)` with no generate_kwargs): no temperature
-    fallback, no `condition_on_prev_tokens`, no no-speech / log-prob / compression thresholds, no prompt.  Every clip
-    keeps a `seek` (in frames of 10 ms); each round decodes the window [seek, seek + 3000) of every unfinished clip as
-    one batch.  What decodes a batch of windows is a parameter, so the loop itself needs no GPU.
+    ASR pipeline passes (R/src/coral/evaluate.py runs `pipeline(...)` with no generate_kwargs): no
+    `condition_on_prev_tokens`, no prompt.  Every clip keeps a `seek` (in frames of 10 ms); each round decodes the window
+    [seek, seek + 3000) of every unfinished clip as one batch.  What decodes a batch of windows is a parameter, so the
+    loop itself needs no GPU;
+  * `FallbackPolicy` / `decode_with_fallback` - `generate_with_fallback`, `_need_fallback`, `_retrieve_compression_ratio`:
+    a window is decoded at temperature 0, scored by average log-probability, compression ratio of its ids and no-speech
+    probability, decoded again with sampling where it fails, and skipped where it is silence.
 
 Times are float64 seconds computed as transformers computes them: offset = seek * time_precision / input_stride,
 time = offset + timestamp_index * time_precision."""
 from __future__ import annotations
+
+import math
+import zlib
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -34,8 +41,117 @@ def check_longform_arguments(other: dict) -> None:
         if neutral is None:
             raise ValueError(f"long-form decoding: argument {name}={val!r} is not known to this build")
         if not any(val is n or (n is not None and type(val) is type(n) and val == n) for n in neutral):
-            raise ValueError(f"long-form decoding: {name}={val!r} is not implemented (greedy windows, each decoded from the "
-                             "forced prefix alone)")
+            hint = "; pass `fallback=FallbackPolicy(...)`" if name in _FALLBACK_NAMES else ""
+            raise ValueError(f"long-form decoding: {name}={val!r} is not implemented as a loose argument (greedy windows, "
+                             f"each decoded from the forced prefix alone){hint}")
+
+
+_FALLBACK_NAMES = ("temperature", "no_speech_threshold", "logprob_threshold", "compression_ratio_threshold")
+
+
+# ---- temperature fallback ----------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class FallbackPolicy:
+    """The arguments of transformers' long-form generate that drive `generate_with_fallback`.  temperatures: tried in
+    order, 0 = greedy, > 0 = sampled; a threshold of None is not checked.  no_speech_threshold needs logprob_threshold (the
+    skip rule is "below the log-prob threshold and above the no-speech threshold") and no_speech_token, the id whose
+    probability at the start-of-transcript position is the no-speech probability.  seed: of the one CPU generator the
+    sampling uniforms are drawn from."""
+    temperatures: tuple = (0.0,)
+    logprob_threshold: float | None = None
+    compression_ratio_threshold: float | None = None
+    no_speech_threshold: float | None = None
+    no_speech_token: int | None = None
+    seed: int = 0
+
+    def __post_init__(self):
+        ts = self.temperatures
+        ts = (ts,) if isinstance(ts, (int, float)) and not isinstance(ts, bool) else tuple(ts)
+        if not ts or any(not isinstance(t, (int, float)) or isinstance(t, bool) or not math.isfinite(t) or t < 0 for t in ts):
+            raise ValueError(f"FallbackPolicy: temperatures must be non-negative finite numbers, got {self.temperatures!r}")
+        object.__setattr__(self, "temperatures", tuple(float(t) for t in ts))
+        if self.no_speech_threshold is not None and (self.logprob_threshold is None or self.no_speech_token is None):
+            raise ValueError("FallbackPolicy: no_speech_threshold needs logprob_threshold and no_speech_token")
+
+    @property
+    def needs_stats(self) -> bool:
+        return self.logprob_threshold is not None
+
+
+def compression_ratio(ids, vocab_size: int) -> float:
+    """`_retrieve_compression_ratio`: raw bytes over zlib-compressed bytes of the ids, int(log2(V) / 8) + 1 little-endian
+    bytes each.  No tokenizer is involved."""
+    length = int(math.log2(vocab_size) / 8) + 1
+    raw = b"".join(int(t).to_bytes(length, "little") for t in ids)
+    return len(raw) / len(zlib.compress(raw))
+
+
+def need_fallback(policy: FallbackPolicy, ids_with_eos, avg_logprob, no_speech_prob, vocab_size: int):
+    """`_need_fallback` -> (needs_fallback, should_skip, compression ratio or None)."""
+    needs, skip, ratio = False, False, None
+    if policy.compression_ratio_threshold is not None:
+        ratio = compression_ratio(ids_with_eos, vocab_size)
+        if ratio > policy.compression_ratio_threshold:
+            needs = True
+    if policy.logprob_threshold is not None and avg_logprob < policy.logprob_threshold:
+        needs = True
+    if policy.no_speech_threshold is not None:
+        if avg_logprob < policy.logprob_threshold and no_speech_prob > policy.no_speech_threshold:
+            needs, skip = False, True
+    return needs, skip, ratio
+
+
+def strip_padding(row, prefix_len: int, pad_id: int, eos_id: int) -> list[int]:
+    """A generated row -> the tokens after the prefix without the padding, the EOS kept ('remove all padding tokens, except
+    for the eos token': the sequence the statistics of `_need_fallback` are taken over)."""
+    gen = [int(t) for t in row[prefix_len:]]
+    if gen and gen[-1] == pad_id:
+        n = sum(1 for t in gen if t == pad_id) - (1 if pad_id == eos_id else 0)
+        if n:
+            gen = gen[:-n]
+    return gen
+
+
+def decode_with_fallback(window_generate, batch, policy: FallbackPolicy, generator, prefix_len: int, pad_id: int,
+                         eos_id: int, vocab_size: int, max_length: int):
+    """`generate_with_fallback` for one batch of windows.  window_generate(batch, temperature, uniforms) -> (rows, stats):
+    id rows as `generate` returns them and dict(sum_logprob, n_scored, no_speech_prob) per row (no_speech_prob may be None
+    without a no-speech threshold); uniforms: float32 [len(batch), max_length] for a sampled attempt, None at temperature
+    0.  Only the rows that failed are decoded again; a row keeps the result of the last attempt it took part in.
+    -> (kept, should_skip): per window of `batch` dict(row, temperature, avg_logprob, compression_ratio, no_speech_prob).
+
+    Restated as the installed transformers runs it, two details included: the flags of an attempt are written at the
+    row's index WITHIN the attempt, and the no-speech probability read for it is that of the window at that index of the
+    whole batch (the detector keeps the inputs of the first attempt).  With one window per batch neither shows."""
+    import torch
+
+    n = len(batch)
+    kept, skip = [None] * n, [False] * n
+    index_map, cur, nsp = list(range(n)), list(batch), None
+    for k, temperature in enumerate(policy.temperatures):
+        uniforms = torch.rand(len(cur), max_length, generator=generator) if temperature > 0 else None
+        rows, stats = window_generate(cur, temperature, uniforms)
+        if len(rows) != len(cur):
+            raise ValueError(f"window_generate returned {len(rows)} rows for {len(cur)} windows")
+        if k == 0 and policy.no_speech_threshold is not None:
+            nsp = [float(p) for p in stats["no_speech_prob"]]
+        next_map, next_cur = [], []
+        for i, row in enumerate(rows):
+            seq = strip_padding(row, prefix_len, pad_id, eos_id)
+            avg = None
+            if policy.needs_stats:
+                avg = float(stats["sum_logprob"][i]) / max(int(stats["n_scored"][i]), 1)
+            needs, skip[i], ratio = need_fallback(policy, seq, avg, None if nsp is None else nsp[i], vocab_size)
+            kept[index_map[i]] = dict(row=row, temperature=temperature, avg_logprob=avg, compression_ratio=ratio,
+                                      no_speech_prob=None if nsp is None else nsp[i])
+            if needs:
+                next_map.append(index_map[i])
+                next_cur.append(cur[i])
+        index_map = next_map
+        if not index_map or k == len(policy.temperatures) - 1:
+            break
+        cur = next_cur
+    return kept, skip
 
 
 def strip_generated(row, prefix_len: int, pad_id: int, eos_id: int) -> list[int]:
@@ -99,16 +215,33 @@ def segments_of(ids, timestamp_begin: int, time_precision: float = TIME_PRECISIO
 
 def run_longform(window_generate, num_frames, timestamp_begin: int, prefix_len: int, pad_id: int, eos_id: int,
                  time_precision: float = TIME_PRECISION, batch_size: int | None = None,
-                 return_token_timestamps: bool | None = False, **other):
+                 return_token_timestamps: bool | None = False, fallback: FallbackPolicy | None = None,
+                 vocab_size: int | None = None, max_length: int | None = None, **other):
     """window_generate([(clip, seek), ...]) -> one generated id row per entry (prefix included, padded as `generate`
     pads).  num_frames: log-mel frames per clip.  -> per clip dict(segments=[(start_s, end_s, ids)], windows=[(seek,
     generated ids)]).  batch_size: at most that many windows per call (None: all unfinished clips at once).
     return_token_timestamps=True: window_generate returns (id rows, float32 times [rows, row length]); segments are
-    (start_s, end_s, ids, token times) and windows (seek, generated ids, their times)."""
+    (start_s, end_s, ids, token times) and windows (seek, generated ids, their times).
+    fallback: a FallbackPolicy; the protocol is then window_generate(batch, temperature, uniforms) -> (rows, stats)
+    (`decode_with_fallback`), vocab_size and max_length are needed, and every clip also carries window_stats: per window
+    dict(seek, temperature, avg_logprob, compression_ratio, no_speech_prob, skipped).  A skipped window advances seek by
+    its frames and contributes no segment."""
     check_longform_arguments(other)
+    generator = None
+    if fallback is not None:
+        import torch
+
+        if return_token_timestamps:
+            raise ValueError("long-form decoding: return_token_timestamps=True is not implemented with fallback=")
+        if vocab_size is None or max_length is None:
+            raise ValueError("long-form decoding: fallback= needs vocab_size and max_length")
+        generator = torch.Generator().manual_seed(int(fallback.seed))
     num_frames = [int(n) for n in num_frames]
     seek = [0] * len(num_frames)
     out = [dict(segments=[], windows=[]) for _ in num_frames]
+    if fallback is not None:
+        for o in out:
+            o["window_stats"] = []
     while True:
         todo = [i for i, n in enumerate(num_frames) if seek[i] < n]
         if not todo:
@@ -116,7 +249,16 @@ def run_longform(window_generate, num_frames, timestamp_begin: int, prefix_len: 
         step = batch_size or len(todo)
         for a in range(0, len(todo), step):
             batch = todo[a:a + step]
-            rows = window_generate([(i, seek[i]) for i in batch])
+            skipped = [False] * len(batch)
+            if fallback is None:
+                rows = window_generate([(i, seek[i]) for i in batch])
+            else:
+                kept, skipped = decode_with_fallback(window_generate, [(i, seek[i]) for i in batch], fallback, generator,
+                                                     prefix_len, pad_id, eos_id, vocab_size, max_length)
+                rows = [k["row"] for k in kept]
+                for i, k, sk in zip(batch, kept, skipped):
+                    out[i]["window_stats"].append(dict(seek=seek[i], skipped=bool(sk),
+                                                       **{n: v for n, v in k.items() if n != "row"}))
             times = [None] * len(batch)
             if return_token_timestamps:
                 rows, times = rows
@@ -124,14 +266,14 @@ def run_longform(window_generate, num_frames, timestamp_begin: int, prefix_len: 
                     raise ValueError(f"window_generate returned {len(times)} rows of token times for {len(rows)} id rows")
             if len(rows) != len(batch):
                 raise ValueError(f"window_generate returned {len(rows)} rows for {len(batch)} windows")
-            for i, row, tt in zip(batch, rows, times):
+            for i, row, tt, sk in zip(batch, rows, times, skipped):
                 gen = strip_generated(row, prefix_len, pad_id, eos_id)
                 frames = min(num_frames[i] - seek[i], WINDOW_FRAMES)
                 offset = seek[i] * time_precision / INPUT_STRIDE
                 if tt is not None:  # (the generated tokens' share of the row's times)
                     tt = np.asarray(tt, dtype=np.float32)[prefix_len:prefix_len + len(gen)]
                 out[i]["windows"].append((seek[i], gen) if tt is None else (seek[i], gen, tt))
-                if not gen:  # (cannot happen under the timestamp rules: the first token is a timestamp)
+                if not gen or sk:  # (empty: cannot happen under the timestamp rules; skipped: silence, no segment)
                     seek[i] += frames
                     continue
                 segs, adv = segments_of(gen, timestamp_begin, time_precision, frames, offset, return_advance=True,

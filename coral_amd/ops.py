@@ -754,6 +754,35 @@ def argmax_timestamps_advance(logits, suppress, out, rows, V, ldv, done, ids, to
                                              _stream()), "ca_argmax_timestamps_advance")
 
 
+def pick_scored_advance(logits, suppress, out, rows, V, ldv, inv_temperature, uniforms, sum_logprob, n_scored, done, ids, tok,
+                        pos, klen, pad_id, eos_id, timestamps=None):
+    """The scored pick of a decoding step with argmax_advance's bookkeeping: greedy (inv_temperature 0) or sampled by
+    inverse CDF on uniforms[r, pos[r] + 1]; the token's log-probability goes to sum_logprob / n_scored.
+    timestamps: (begin_index, timestamp_begin, max_initial_timestamp_index) for Whisper's timestamp rules over the history
+    in `ids`, None for the suppress mask alone."""
+    if done.dtype != torch.bool or ids.dtype != torch.int64 or ids.dim() != 2 or ids.stride(1) != 1:
+        raise CoralAmdError("pick_scored_advance: done must be bool, ids a row-major int64 matrix")
+    if sum_logprob.dtype != torch.float32 or n_scored.dtype != torch.int32 or pos.dtype != torch.int32:
+        raise CoralAmdError("pick_scored_advance: sum_logprob must be float32, n_scored and pos int32")
+    ld_u = 0
+    if inv_temperature > 0:
+        if uniforms is None or uniforms.dtype != torch.float32 or uniforms.dim() != 2 or uniforms.stride(1) != 1 \
+                or uniforms.shape[0] < rows:
+            raise CoralAmdError("pick_scored_advance: sampling needs uniforms, a row-major float32 matrix [rows, length]")
+        ld_u = uniforms.stride(0)
+    begin, tb, cap = timestamps if timestamps is not None else (0, 0, None)
+    check(lib().ca_pick_scored_advance(_p(logits), _p(suppress), _p(out), rows, V, ldv, float(inv_temperature), _p(uniforms),
+                                       ld_u, _p(sum_logprob), _p(n_scored), done.data_ptr(), _p(ids), ids.stride(0), _p(tok),
+                                       _p(pos), _p(klen), int(pad_id), int(eos_id),
+                                       _p(ids) if timestamps is not None else None, int(begin), int(tb), _cap(cap), _stream()),
+          "ca_pick_scored_advance")
+
+
+def row_token_prob(logits, out, rows, V, ldv, token):
+    """out[r] = softmax(logits[r, :V])[token] in fp32 over the raw row."""
+    check(lib().ca_row_token_prob(_p(logits), _p(out), rows, V, ldv, int(token), _stream()), "ca_row_token_prob")
+
+
 ALIGN_WS_CAP_BYTES = 64 << 20  # fp32 scratch of ca_whisper_align_cost: clips are grouped to stay below it (DESIGN.md §8)
 
 

@@ -533,7 +533,7 @@ class WhisperEngine:
         (csrc/decode.hip), the timestamp rules live in ca_argmax_timestamps_advance."""
         if "persist" in g:
             return g["persist"]
-        if g.get("ts") is not None:
+        if g.get("ts") is not None or g.get("scored") is not None:  # (the scored pick is a launch of its own as well)
             g["persist"] = None
             return None
         s, st = self.s, self.store
@@ -665,6 +665,12 @@ class WhisperEngine:
         V, Vp = s.vocab_size, _r8(s.vocab_size)
         # argmax + the step's bookkeeping in one launch: out[b, pos + 1] = the token (pad for finished rows), done |= eos,
         # tok = the token, pos += 1, klen += 1
+        if g.get("scored") is not None:  # greedy or sampled, with the token's log-probability (csrc/sample.hip)
+            sc = g["scored"]
+            ops.pick_scored_advance(g["logits"], suppress, g["nxt"], B, V, Vp, sc["inv_t"], sc["uniforms"], sc["sum_logprob"],
+                                    sc["n_scored"], g["done"], g["out"], g["tok"], g["pos"], g["klen"], g["pad_id"], g["eos"],
+                                    timestamps=g.get("ts"))
+            return
         if g.get("ts") is not None:  # the same step under the timestamp rules (history: g["out"] up to g["pos"])
             begin, tb, cap = g["ts"]
             ops.argmax_timestamps_advance(g["logits"], suppress, g["nxt"], B, V, Vp, g["done"], g["out"], g["tok"], g["pos"],
@@ -699,7 +705,8 @@ class WhisperEngine:
                  length_penalty: float = 1.0, early_stopping: bool = False, return_trace: bool = False,
                  _beam_path: bool = False, return_timestamps: bool = False, timestamp_begin: int | None = None,
                  max_initial_timestamp_index: int | None = None, return_token_timestamps: bool = False,
-                 alignment_heads=None, num_frames=None, median_filter_width: int = 7):
+                 alignment_heads=None, num_frames=None, median_filter_width: int = 7, temperature: float = 0.0,
+                 sample_uniforms=None, return_stats: bool = False, no_speech_token: int | None = None, cross_kv=None):
         """Greedy decoding with a forced prefix (<|sot|><|da|><|transcribe|><|notimestamps|> in CoRal's
         evaluation): masked argmax on the GPU (ca_argmax_masked), stop at EOS / max_length.
         num_beams = k >= 2: beam search (`_generate_beam`; length_penalty, early_stopping True / False as in
@@ -710,10 +717,42 @@ class WhisperEngine:
         generation config's or None).  Not with beams; the one-launch-per-token kernel is bypassed.
         return_token_timestamps=True (with return_timestamps=True, greedy only): -> (ids, times), times float32 seconds
         [B, len(ids[0])] from the cross-attention of `alignment_heads` [(layer, head)] and dynamic time warping
-        (`token_timestamps`); num_frames: valid log-mel frames per clip (None: all)."""
+        (`token_timestamps`); num_frames: valid log-mel frames per clip (None: all).
+        temperature > 0: every pick is sampled by inverse CDF at that temperature on `sample_uniforms` (float32
+        [B, max_length], the uniform of position p in column p; ca_pick_scored_advance).  return_stats=True: -> (ids,
+        dict(sum_logprob, n_scored, no_speech_prob)) per clip: the log-probabilities of the generated tokens (EOS included)
+        under the processed distribution at temperature 1 and their count; with `no_speech_token`, the probability of that
+        id at the first prefix position.  Either keeps the launch sequence (graph-captured per token); not with beams.
+        cross_kv: the result of `cross_kv(encode(...))` (or `gather_cross_kv` of it) - the encoder is then not run and
+        input_features may be None."""
         s, dev = self.s, self.device
         beam = num_beams != 1 or _beam_path
         ts = None
+        scored = None
+        if temperature is None or not isinstance(temperature, (int, float)) or isinstance(temperature, bool) \
+                or not math.isfinite(temperature) or temperature < 0:
+            raise ValueError(f"temperature must be a non-negative finite number, got {temperature!r}")
+        if temperature > 0 or return_stats or no_speech_token is not None:
+            if beam:
+                what = f"temperature={temperature}" if temperature > 0 else "return_stats=True"
+                raise ValueError(f"generate(num_beams={num_beams}): {what} is not implemented with beam search")
+            if return_token_timestamps:
+                raise ValueError("return_token_timestamps=True is not implemented with temperature > 0 / return_stats=True")
+            if not use_cache:
+                raise ValueError("temperature > 0 / return_stats=True need use_cache=True")
+            if max_length <= len(prefix) or max_length > s.max_target_positions:
+                raise ValueError(f"temperature > 0 / return_stats=True need len(prefix) < max_length <= "
+                                 f"{s.max_target_positions}, got {max_length}")
+            if temperature > 0:
+                if sample_uniforms is None:
+                    raise ValueError(f"temperature={temperature} needs sample_uniforms, float32 [clips, max_length]")
+                if sample_uniforms.dim() != 2 or sample_uniforms.shape[1] < max_length:
+                    raise ValueError(f"sample_uniforms must be [clips, >= max_length], got {tuple(sample_uniforms.shape)}")
+            if no_speech_token is not None and not 0 <= no_speech_token < s.vocab_size:
+                raise ValueError(f"no_speech_token={no_speech_token} lies outside the vocabulary")
+            scored = dict(inv_t=float(np.float32(1.0 / temperature)) if temperature > 0 else 0.0,
+                          uniforms=sample_uniforms if temperature > 0 else None, no_speech_token=no_speech_token,
+                          use_graph=use_graph)
         if return_token_timestamps:
             from .whisper_align import check_alignment_heads
 
@@ -744,9 +783,15 @@ class WhisperEngine:
                                  "through CaAttnDesc.key_slot)")
         elif return_trace:
             raise ValueError("return_trace is a beam search option (num_beams >= 2)")
-        enc = self.encode(input_features)
-        kv = self.cross_kv(enc)
-        B = enc.shape[0]
+        if cross_kv is not None:
+            if not use_cache:
+                raise ValueError("cross_kv= needs use_cache=True (the pass without a cache reads the encoder states)")
+            kv, enc = cross_kv, None
+            B = kv[0].numel() // (s.max_source_positions * 2 * s.d_model)
+        else:
+            enc = self.encode(input_features)
+            kv = self.cross_kv(enc)
+            B = enc.shape[0]
         V = s.vocab_size
         sup = torch.zeros(V, dtype=torch.uint8, device=dev)
         if suppress_tokens:
@@ -757,6 +802,13 @@ class WhisperEngine:
         if beam:
             return self._generate_beam(kv, prefix, max_length, sup, sup_begin, num_beams, float(length_penalty),
                                        bool(early_stopping), return_trace, use_graph)
+        if scored is not None:
+            if temperature > 0 and sample_uniforms.shape[0] != B:
+                raise ValueError(f"sample_uniforms has {sample_uniforms.shape[0]} rows for {B} clips")
+            rows = self._generate_graph(kv, prefix, max_length, sup, sup_begin, ts, scored)
+            stats = dict(sum_logprob=scored["sum_logprob"].cpu().tolist(), n_scored=scored["n_scored"].cpu().tolist(),
+                         no_speech_prob=scored["no_speech_prob"].cpu().tolist() if no_speech_token is not None else None)
+            return (rows, stats) if return_stats else rows
         if use_cache and use_graph and max_length > len(prefix) + 2:
             rows = self._generate_graph(kv, prefix, max_length, sup, sup_begin, ts)
             if return_token_timestamps:
@@ -850,7 +902,14 @@ class WhisperEngine:
         times = times_from_jumps(jump.cpu().numpy(), prefix_len, Ltot)
         return (times, dict(cost=cost, jump=jump, frames=frames)) if return_parts else times
 
-    def _generate_graph(self, kv, prefix, max_length, sup, sup_begin, ts=None):
+    def gather_cross_kv(self, kv: list, rows) -> list:
+        """The cross K|V of a subset of the clips of `cross_kv`'s result (a fallback attempt decodes the rows that failed
+        against the K|V of the window's one encoder pass)."""
+        n = self.s.max_source_positions * 2 * self.s.d_model
+        idx = torch.as_tensor(list(rows), dtype=torch.int64, device=self.device)
+        return [c.view(-1, n).index_select(0, idx).reshape(-1) for c in kv]
+
+    def _generate_graph(self, kv, prefix, max_length, sup, sup_begin, ts=None, scored=None):
         """Greedy loop with the per-token step captured once in a HIP graph and replayed: the ~350 small
         launches of a token (24-32 layers x 14 kernels) cost one graph launch instead of 350 host calls."""
         s, dev = self.s, self.device
@@ -861,17 +920,41 @@ class WhisperEngine:
         # the forced prefix and the first free token run eagerly (different shapes / begin-suppress mask)
         ids0 = torch.tensor([prefix] * B, dtype=torch.int64, device=dev)
         base = self.decode_step(ids0, kv, cache).contiguous()
-        if ts is None:
+        if scored is not None:
+            g["scored"] = scored
+            scored["sum_logprob"] = torch.zeros(B, dtype=torch.float32, device=dev)
+            scored["n_scored"] = torch.zeros(B, dtype=torch.int32, device=dev)
+            if scored["uniforms"] is not None:
+                scored["uniforms"] = scored["uniforms"].to(dev, torch.float32).contiguous()
+            if scored["no_speech_token"] is not None:
+                # WhisperNoSpeechDetection: the softmax of the raw logits at the start-of-transcript position, i.e. the
+                # head on prefix position 0 (decode_step left the final LayerNorm of every prefix row in the workspace)
+                hf0 = self._decoder_ws(B, P)["hf"][:B * P * s.d_model].view(B, P, s.d_model)[:, 0, :].contiguous()
+                lg0 = torch.empty(B, _r8(V), dtype=torch.float32, device=dev)
+                ops.gemm(hf0, self.store.p16, lg0, M=B, N=V, K=s.d_model, lda=s.d_model, ldb=s.d_model, ldc=_r8(V),
+                         b_off=self.store.off("model.decoder.embed_tokens.weight"))
+                scored["no_speech_prob"] = torch.empty(B, dtype=torch.float32, device=dev)
+                ops.row_token_prob(lg0, scored["no_speech_prob"], B, V, _r8(V), scored["no_speech_token"])
+            # the first free token through the scored pick as well (its log-probability counts): the books stand at the
+            # last prefix token
+            g["out"][:, :P] = ids0
+            g["pos"].fill_(P - 1)
+            g["klen"].fill_(P)
+            ops.pick_scored_advance(base, sup_begin, g["nxt"], B, V, V, scored["inv_t"], scored["uniforms"],
+                                    scored["sum_logprob"], scored["n_scored"], g["done"], g["out"], g["tok"], g["pos"], g["klen"],
+                                    s.pad_token_id, s.eos_token_id, timestamps=ts)
+        elif ts is None:
             ops.argmax_masked(base, sup_begin, g["nxt"], B, V, V)
         else:  # (an empty history: only the prefix length matters)
             ops.argmax_timestamps(base, sup_begin, g["nxt"], B, V, V, ids0, torch.full((B,), P - 1, dtype=torch.int32, device=dev),
                                   ts[0], ts[1], s.eos_token_id, ts[2])
-        g["out"][:, :P] = ids0
-        g["out"][:, P] = g["nxt"].long()
-        g["done"] |= g["nxt"] == s.eos_token_id
-        g["tok"].copy_(g["nxt"])
-        g["pos"].fill_(P)
-        g["klen"].fill_(P + 1)
+        if scored is None:
+            g["out"][:, :P] = ids0
+            g["out"][:, P] = g["nxt"].long()
+            g["done"] |= g["nxt"] == s.eos_token_id
+            g["tok"].copy_(g["nxt"])
+            g["pos"].fill_(P)
+            g["klen"].fill_(P + 1)
         g["cur"].fill_(P + 1)
         n_done = P + 1
         if n_done < max_length and not bool(g["done"].all()):
@@ -880,6 +963,8 @@ class WhisperEngine:
         graphs = {}
 
         def replay(n):  # n token steps as ONE graph (capture records the launches without running them)
+            if scored is not None and not scored["use_graph"]:
+                return self._token_step(cache, g, sup)
             if n not in graphs:
                 torch.cuda.synchronize()
                 graphs[n] = torch.cuda.CUDAGraph()
@@ -932,7 +1017,7 @@ class WhisperEngine:
                 warnings.warn("coral_amd: " + msg + "; decoding this batch again as a launch sequence and keeping that "
                               "path for this engine (CA_DECODE_STRICT=1 raises instead)")
                 self._persistent_off = True
-                return self._generate_graph(kv, prefix, max_length, sup, sup_begin, ts)
+                return self._generate_graph(kv, prefix, max_length, sup, sup_begin, ts, scored)
         # trim like the eager loop: stop at the first column where every row had already finished
         fin = (out == s.eos_token_id).cumsum(1) > 0
         allfin = fin.all(0)

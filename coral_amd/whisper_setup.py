@@ -235,19 +235,38 @@ class WhisperForConditionalGeneration:
 
     def generate(self, input_features, language="danish", task="transcribe", max_length: int = 225, num_beams: int | None = 1,
                  length_penalty: float = 1.0, early_stopping=False, return_timestamps: bool | None = False,
-                 return_token_timestamps: bool | None = False, num_frames=None, **other):
+                 return_token_timestamps: bool | None = False, num_frames=None, temperature=None, logprob_threshold=None,
+                 compression_ratio_threshold=None, no_speech_threshold=None, sample_seed: int = 0,
+                 return_fallback_stats: bool = False, **other):
         """Greedy (num_beams 1 / None: other keyword arguments are ignored, as before) or beam search (num_beams >= 2,
         transformers' semantics; every generation argument this build does not implement is then refused by name).
         return_timestamps=True (greedy only): the prefix drops <|notimestamps|> and every pick obeys Whisper's timestamp
         rules (timestamp_begin = that id + 1, max_initial_timestamp_index from the generation config).
         return_token_timestamps=True (with return_timestamps=True, greedy only): -> (ids, float32 seconds per token) from
         the cross-attention of the generation config's `alignment_heads` (absent: transformers' error) and dynamic time
-        warping; num_frames: valid log-mel frames per clip; `median_filter_width` is the checkpoint config's (default 7)."""
+        warping; num_frames: valid log-mel frames per clip; `median_filter_width` is the checkpoint config's (default 7).
+        temperature (a number or a tuple tried in order), logprob_threshold, compression_ratio_threshold,
+        no_speech_threshold, sample_seed: transformers' temperature fallback for clips of one window (greedy only, no token
+        timestamps): `decode_with_fallback` of coral_amd/longform_whisper.py with one window per clip, the encoder run once.
+        A clip skipped as silence comes back as the prefix and EOS.  return_fallback_stats=True: -> (ids, per clip
+        dict(temperature, avg_logprob, compression_ratio, no_speech_prob, skipped))."""
         if language not in ("danish", "da") or task != "transcribe":
             raise ValueError("only language='danish', task='transcribe' (CoRal's evaluation call) is wired up")
         prefix = self.forced_prefix()
         num_beams = 1 if num_beams is None else num_beams
         kw = {}
+        policy = None
+        if num_beams != 1:  # with beams they are refused by name below, their neutral values pass as before
+            given = dict(temperature=temperature, logprob_threshold=logprob_threshold,
+                         compression_ratio_threshold=compression_ratio_threshold, no_speech_threshold=no_speech_threshold)
+            other = dict(other, **{k: v for k, v in given.items() if v is not None})
+        else:
+            policy = self.fallback_policy(temperature, logprob_threshold, compression_ratio_threshold, no_speech_threshold,
+                                          sample_seed)
+        if policy is not None and return_token_timestamps:
+            raise ValueError("return_token_timestamps=True is not implemented with temperature fallback")
+        if policy is None and return_fallback_stats:
+            raise ValueError("return_fallback_stats=True needs temperature= or a threshold (greedy only)")
         if return_timestamps:
             if num_beams != 1:
                 other = dict(other, return_timestamps=return_timestamps)  # refused by name below
@@ -271,8 +290,63 @@ class WhisperForConditionalGeneration:
             check_beam_arguments(int(input_features.shape[0]), num_beams, length_penalty, early_stopping, other)
             kw = dict(num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping)
         # CoRal clears `suppress_tokens`; the default begin-suppress set (blank ' ' = 220, eos) stays
+        if policy is not None:
+            from .longform_whisper import decode_with_fallback
+
+            s = self.shape
+            n = int(input_features.shape[0])
+            attempt = self.fallback_attempts(policy, max_length, bool(return_timestamps))
+            feats = {(i, 0): input_features[i] for i in range(n)}
+            kept, skipped = decode_with_fallback(lambda batch, t, u: attempt(batch, t, u, feats), [(i, 0) for i in range(n)],
+                                                 policy, torch.Generator().manual_seed(int(policy.seed)), len(prefix),
+                                                 s.pad_token_id, s.eos_token_id, s.vocab_size, max_length)
+            rows = [list(prefix) + [s.eos_token_id] if sk else [int(t) for t in k["row"]] for k, sk in zip(kept, skipped)]
+            width = max(len(r) for r in rows)
+            rows = [r + [s.pad_token_id] * (width - len(r)) for r in rows]
+            if not return_fallback_stats:
+                return rows
+            return rows, [dict(skipped=bool(sk), **{a: v for a, v in k.items() if a != "row"}) for k, sk in zip(kept, skipped)]
         return self.engine.generate(input_features, prefix, max_length, suppress_tokens=None,
                                     begin_suppress_tokens=[220, self.shape.eos_token_id], **kw)
+
+    def fallback_policy(self, temperature=None, logprob_threshold=None, compression_ratio_threshold=None,
+                        no_speech_threshold=None, sample_seed: int = 0):
+        """The FallbackPolicy of these generate arguments, or None where they leave decoding as it is (temperature None
+        / 0 / (0,) and no threshold).  <|nospeech|> is the id in front of <|notimestamps|>, as transformers takes it."""
+        from .longform_whisper import FallbackPolicy
+
+        ts = (0.0,) if temperature is None else temperature
+        ts = (ts,) if isinstance(ts, (int, float)) and not isinstance(ts, bool) else tuple(ts)
+        if all(t == 0 for t in ts) and len(ts) <= 1 and logprob_threshold is None and compression_ratio_threshold is None \
+                and no_speech_threshold is None:
+            return None
+        return FallbackPolicy(ts, logprob_threshold, compression_ratio_threshold, no_speech_threshold,
+                              self.forced_prefix()[-1] - 1 if no_speech_threshold is not None else None, int(sample_seed))
+
+    def fallback_attempts(self, policy, max_length: int, return_timestamps: bool):
+        """-> attempt(batch, temperature, uniforms, feats): the `window_generate` of `decode_with_fallback` on this model.
+        batch: keys of `feats` (key -> log-mel [mels, 3000]).  The encoder and the cross K|V run when a batch brings keys
+        that the last encoded batch did not hold; a later attempt decodes its rows against a gather of that K|V."""
+        eng, s = self.engine, self.shape
+        prefix = self.forced_prefix(return_timestamps)
+        kw = {}
+        if return_timestamps:
+            kw = dict(return_timestamps=True, timestamp_begin=self.forced_prefix()[-1] + 1,
+                      max_initial_timestamp_index=self.generation_config.get("max_initial_timestamp_index", None))
+        held = dict(keys={}, kv=None)
+
+        def attempt(batch, temperature, uniforms, feats):
+            if held["kv"] is None or any(k not in held["keys"] for k in batch):
+                held["kv"] = eng.cross_kv(eng.encode(torch.stack([torch.as_tensor(feats[k]) for k in batch])))
+                held["keys"] = {k: i for i, k in enumerate(batch)}
+            rows = [held["keys"][k] for k in batch]
+            kv = held["kv"] if rows == list(range(len(held["keys"]))) else eng.gather_cross_kv(held["kv"], rows)
+            return eng.generate(None, prefix, max_length, suppress_tokens=None,
+                                begin_suppress_tokens=[220, s.eos_token_id], temperature=float(temperature),
+                                sample_uniforms=uniforms, return_stats=True, no_speech_token=policy.no_speech_token,
+                                cross_kv=kv, **kw)
+
+        return attempt
 
 
 class WhisperModelSetup(ModelSetup):

@@ -732,6 +732,28 @@ int ca_argmax_timestamps_advance(const float* logits, const uint8_t* suppress, i
                                  int64_t ldv, uint8_t* done, int64_t* ids, int64_t ld_ids, int32_t* tok, int32_t* pos,
                                  int32_t* klen, int32_t pad_id, int32_t eos_id, int32_t begin_index,
                                  int32_t timestamp_begin, int32_t max_initial_timestamp_index, void* stream);
+/* The scored pick of Whisper's temperature fallback (csrc/sample.hip; generate_with_fallback,
+ * $TF/models/whisper/generation_whisper.py): one launch per token with the bookkeeping of ca_argmax_advance, all state in
+ * device memory.  The allowed set of a row: with `history` (normally `ids` itself, leading dimension ld_ids) what
+ * ca_argmax_timestamps leaves - suppress mask, text and timestamp windows, and no text at all if
+ * logsumexp(timestamps) > max(text); with history == NULL what the suppress mask leaves.
+ *   inv_temperature == 0: the token is the first maximum, the bits of ca_argmax_timestamps_advance / ca_argmax_advance.
+ *   inv_temperature  > 0: p_i = exp((x_i - m) * inv_temperature) over the allowed set (m its maximum, fp32), S = sum p_i,
+ *     target = u * S with u = uniforms[r * ld_u + pos[r] + 1] (fp32 [rows, ld_u], indexed by the position written); the
+ *     token is the smallest allowed i with p_i > 0 whose inclusive prefix sum exceeds target, and the last allowed i
+ *     with p_i > 0 where rounding leaves none.  The summation order is fixed (no atomics) and no prefix value sits behind
+ *     more than 41 fp32 additions (V <= 262144).
+ * Both modes: logprob = x_tok - logsumexp(allowed set at temperature 1) (`_retrieve_avg_logprobs`); a row that was not
+ * done before the step adds it to sum_logprob[r] and 1 to n_scored[r] (EOS counts); a finished row takes pad_id and adds
+ * nothing.  out[r] = the token picked.  ldv == 0: every row reads the same logits. */
+int ca_pick_scored_advance(const float* logits, const uint8_t* suppress, int32_t* out, int64_t rows, int32_t V, int64_t ldv,
+                           float inv_temperature, const float* uniforms, int64_t ld_u, float* sum_logprob,
+                           int32_t* n_scored, uint8_t* done, int64_t* ids, int64_t ld_ids, int32_t* tok, int32_t* pos,
+                           int32_t* klen, int32_t pad_id, int32_t eos_id, const int64_t* history, int32_t begin_index,
+                           int32_t timestamp_begin, int32_t max_initial_timestamp_index, void* stream);
+/* out[r] = softmax(logits[r, :V])[token], fp32, over the raw row: the no-speech probability of WhisperNoSpeechDetection
+ * ($TF/generation/logits_process.py) when the row is the start-of-transcript position of the prefix. */
+int ca_row_token_prob(const float* logits, float* out, int64_t rows, int32_t V, int64_t ldv, int32_t token, void* stream);
 /* embedding gather: y[r,:] = table[ids[r],:] + pos[pos_ids[r],:]  (bf16 tables)
  * $TF/models/whisper/modeling_whisper.py:204-212,676. */
 int ca_embed_tokens(const void* table, const void* pos, const int32_t* ids,

@@ -342,8 +342,10 @@ def test_greedy_decode_bit_exact(ops, golden_dir):
     tie = torch.zeros(1, 4, Vp)
     tie[0, :, 5] = 1.0
     tie[0, :, 9] = 1.0
-    ops.ctc_greedy_decode(tie.to(DEV), None, raw[:1, :4].contiguous(), ids[:1, :4].contiguous(), olen[:1], 1, 4,
-                          V, Vp, 45)
+    traw, tids = raw[:1, :4].contiguous(), ids[:1, :4].contiguous()
+    ops.ctc_greedy_decode(tie.to(DEV), None, traw, tids, olen[:1], 1, 4, V, Vp, 45)
+    assert (traw == 5).all()
+    assert int(tids[0, 0]) == 5 and int(olen[0]) == 1 and (tids[0, 1:] == -1).all()
 
 
 def test_posconv_weight_fwd_bwd(ops):

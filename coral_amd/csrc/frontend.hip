@@ -142,6 +142,14 @@ template <>
 __device__ __forceinline__ float pcm_load<float>(const float* p, int64_t i) { return p[i]; }
 template <>
 __device__ __forceinline__ float pcm_load<int16_t>(const int16_t* p, int64_t i) { return (float)p[i] * (1.0f / 32768.0f); }
+// The gained sample as a rounded product of its own.  Fused into the subtraction of the mean (fma(v, gain, -mean)) it
+// would be the exact product there while the mean was formed from the rounded one: an utterance of one sample
+// then comes out as the product's rounding error times rsqrt(eps) (~1e-4) where it must be exactly 0.
+template <typename T>
+__device__ __forceinline__ float pcm_gained(const T* p, int64_t i, float gain) {
+#pragma clang fp contract(off)
+  return pcm_load<T>(p, i) * gain;
+}
 
 template <typename T>
 __global__ __launch_bounds__(1024) void pcm_prepare_kernel(const T* __restrict__ pcm, int64_t ld_in,
@@ -185,7 +193,7 @@ __global__ __launch_bounds__(1024) void pcm_prepare_kernel(const T* __restrict__
   if (znorm) {
     float s2 = 0.f;
     for (int64_t i = threadIdx.x; i < len; i += 1024) {
-      const float d = pcm_load<T>(xb, i) * gain - mean;
+      const float d = pcm_gained<T>(xb, i, gain) - mean;
       s2 += d * d;
     }
     s2 = wave_sum(s2);
@@ -202,7 +210,7 @@ __global__ __launch_bounds__(1024) void pcm_prepare_kernel(const T* __restrict__
     shift = mean;
   }
   for (int64_t i = threadIdx.x; i < N; i += 1024) {
-    yb[i] = i < len ? (pcm_load<T>(xb, i) * gain - shift) * rstd : 0.f;
+    yb[i] = i < len ? (pcm_gained<T>(xb, i, gain) - shift) * rstd : 0.f;
     if (mask) mask[(int64_t)b * N + i] = i < len ? 1 : 0;
   }
 }

@@ -395,7 +395,7 @@ def wgrad_stream(engine):
     CA_WGRAD_STREAM=0)."""
     if os.environ.get("CA_WGRAD_STREAM", "1") == "0":
         return None
-    if getattr(engine, "_wstream", None) is None:
+    if engine._wstream is None:
         engine._wstream = ops.side_stream(engine.device, "wgrad", int(os.environ.get("CA_WGRAD_PRIO", "0")))
     return engine._wstream
 

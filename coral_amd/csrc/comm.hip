@@ -1,7 +1,7 @@
 // Data-parallel exchange behind the C ABI: bucket collectives over RCCL (xGMI) on a communication stream owned by an
 // explicit context - what accelerate's DDP wrapper / DeepSpeed ZeRO-2 do for the reference
 // (accelerate/accelerator.py:1892 prepare_model -> DistributedDataParallel, :2053 backward; R/makefile:79-84), reachable
-// from any host language: the Python host (coral_amd/trainer.py) calls these through ctypes, torch.distributed stays for
+// from any host language: the Python host (coral_amd/exchange.py) calls these through ctypes, torch.distributed stays for
 // the rendezvous (handing rank 0's unique id to the other ranks) and for the gloo CPU tests.
 //
 // RCCL is bound at run time (dlopen "librccl.so.1" on the first ca_comm_* call): the library loads, and every kernel

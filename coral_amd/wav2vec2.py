@@ -28,7 +28,8 @@ from dataclasses import dataclass
 import torch
 
 from . import ops
-from .blocks import FFNBlock, Scratch, SelfAttnBlock, encoder_backward, layernorm_bwd, norm_plan, wgrad_stream
+from .blocks import FFNBlock, Scratch, SelfAttnBlock, encoder_backward, layernorm_bwd, wgrad_stream
+from .engine import Engine
 from .staging import PinnedStager
 from .ops import EPI_GELU_RESIDUAL, EPI_RESIDUAL, MNMAJOR
 
@@ -156,7 +157,8 @@ class ParamStore:
     def view(self, name: str, which: str = "p32") -> torch.Tensor:
         off, shape = self.index[name]
         n = int(math.prod(shape))
-        return getattr(self, which)[off:off + n].view(shape)
+        buf = self.g16 if which == "g16" else vars(self)[which]  # (p32 / g32 / p16; g16 is allocated on first use)
+        return buf[off:off + n].view(shape)
 
     def names(self):
         return list(self.index.keys())
@@ -236,7 +238,7 @@ DROPOUT_SITES = {"attention": (1, "attention_dropout"), "attn_out": (2, "hidden_
                  "pos_conv": (5, "hidden_dropout"), "final": (6, "final_dropout")}
 
 
-class Wav2Vec2CTCEngine:
+class Wav2Vec2CTCEngine(Engine):
     """Forward + backward of Wav2Vec2ForCTC as a fixed sequence of HIP kernels."""
 
     def __init__(self, shape: Wav2Vec2Shape, device="cuda:0", freeze_base: bool = False):
@@ -264,16 +266,15 @@ class Wav2Vec2CTCEngine:
                 FFNBlock(self.store, p + "final_layer_norm", p + "feed_forward.intermediate_dense",
                          p + "feed_forward.output_dense", s.hidden_size, s.intermediate_size, s.layer_norm_eps)))
         self.freeze_base = freeze_base
-        self.training = False
         # packed mode (forward()): the encoder of a training step works on the valid frames only
         self.pack_frames = os.environ.get("CA_PACK_FRAMES", "0") not in ("", "0")
         self.last_rows = 0  # rows the encoder layers processed in the last forward: sum(flen) when packed, else B * T
         self.last_frames = 0  # ... and B * T of that forward
         self._ws = None
         self._ws_key = None
+        self._ctc_key = None
         self._stager = PinnedStager(self.device)
         self._saved = None
-        self.step_seed = 0
         d = s.hidden_size
         G = s.num_conv_pos_embedding_groups
         K = s.num_conv_pos_embeddings
@@ -342,16 +343,6 @@ class Wav2Vec2CTCEngine:
     def grad_dict(self) -> dict:
         return {n: self.store.view(n, "g32") for n in self.store.names()}
 
-    # The trainer may still be updating parameter buckets on its optimiser stream when the next forward
-    # starts (trainer.py: the HBM-bound AdamW overlaps the MFMA-bound forward); the forward waits for a
-    # bucket's event right before the first kernel that reads its weights.
-    weights_ready: dict | None = None
-
-    def _await(self, bucket: str):
-        ev = self.weights_ready.get(bucket) if self.weights_ready else None
-        if ev is not None:
-            torch.cuda.current_stream().wait_event(ev)
-
     # the four weight matrices of an encoder layer: (first parameter name, rows, columns)
     def _layer_matrices(self, l: int):
         d, f = self.s.hidden_size, self.s.intermediate_size
@@ -360,15 +351,9 @@ class Wav2Vec2CTCEngine:
                 ("fc1", pl + "feed_forward.intermediate_dense.weight", f, d),
                 ("fc2", pl + "feed_forward.output_dense.weight", d, f)]
 
-    def norm_plan(self):
-        """Squared gradient norm without a pass over the layer weight matrices (>99 % of the buffer; blocks.norm_plan).
-        None when the model is frozen up to the head (the norm then covers the head bucket only)."""
-        if self.freeze_base:
-            return None
-        if getattr(self, "_norm_plan", None) is None:
-            self._norm_plan = norm_plan(self.store, [(l, *m) for l in range(self.s.num_hidden_layers)
-                                                     for m in self._layer_matrices(l)], self.device)
-        return self._norm_plan
+    def norm_matrices(self):
+        """Every layer's weight matrices (>99 % of the buffer): the gradient norm needs no pass over them."""
+        return [(l, *m) for l in range(self.s.num_hidden_layers) for m in self._layer_matrices(l)]
 
     def shard_ranges(self) -> dict:
         """{layer bucket: (first element of its weight matrices, bucket end)}: the part of every layer bucket a sharded
@@ -391,30 +376,28 @@ class Wav2Vec2CTCEngine:
         st = self.store
         if matrices:
             st.g32.zero_()
-            self._pre_zeroed = False
+            self.pre_zeroed = False
             return
-        if getattr(self, "_pre_zeroed", False):
+        if self.pre_zeroed:
             # the trainer already cleared these slices on its optimiser stream, right behind the AdamW launches that
             # consumed them (hidden under the forward instead of sitting in front of the backward)
-            self._pre_zeroed = False
+            self.pre_zeroed = False
             return
         self.clear_small_grads()
+
+    preclear_small_grads = True
 
     def clear_small_grads(self):
         """Zero everything except the transformer layers' weight matrices (see zero_grad): the front and head
         buckets and every layer's small tensors (LayerNorms, biases), as ONE launch over a cached range table."""
         st = self.store
-        if getattr(self, "_small_ranges", None) is None:
+        if self._small_ranges is None:
             rs = [(lo, hi - lo) for lo, hi in (st.buckets[n] for n in ("front", "head"))]
             for l in range(self.s.num_hidden_layers):
                 lo = st.off(f"wav2vec2.encoder.layers.{l}.layer_norm.weight")
                 rs.append((lo, st.off(f"wav2vec2.encoder.layers.{l}.attention.q_proj.weight") - lo))
             self._small_ranges = tuple(rs)
         ops.clear_ranges(st.g32, self._small_ranges)
-
-    def train(self, mode: bool = True):
-        self.training = mode
-        return self
 
     def dropout_site(self, site: str, l: int = 0, training: bool | None = None) -> tuple:
         """(p, seed) of one dropout site (DROPOUT_SITES) of layer l in the current step; (0.0, 0) outside training or
@@ -423,13 +406,11 @@ class Wav2Vec2CTCEngine:
         Seeds: step_seed * 1000 + 100 * code + l.  The activation dropout of layer l keeps step_seed * 1000 + l, so the
         sites and layers of one step draw from disjoint seeds (l < 100), and no seed of one step is one of another."""
         code, key = DROPOUT_SITES[site]
-        p = float(getattr(self.s, key)) if (self.training if training is None else training) else 0.0
+        shape = self.s
+        p = float(getattr(shape, key)) if (self.training if training is None else training) else 0.0
         if p <= 0.0:
             return 0.0, 0
         return p, self.step_seed * 1000 + 100 * code + l
-
-    def eval(self):
-        return self.train(False)
 
     def refresh_compute_weights(self):
         """fp32 masters -> bf16 copies, conv weight reorders, weight-normed pos-conv weights."""
@@ -692,7 +673,7 @@ class Wav2Vec2CTCEngine:
             Lmax = lab.shape[1]
             in_len = flen
             key = (B, T, Lmax)
-            if getattr(self, "_ctc_key", None) != key:
+            if self._ctc_key != key:
                 self._ctc_ws = torch.zeros(ops.ctc_workspace_bytes(B, T, Lmax), dtype=torch.uint8, device=dev)
                 self._ctc_key = key
             gscale = None
@@ -733,7 +714,7 @@ class Wav2Vec2CTCEngine:
         # ... and, when they are overwritten (one micro-batch per optimiser step) and the trainer asked for it, kept in
         # bf16: the reference's autocast computes a Linear's weight gradient as a bf16 matmul output and only casts it to
         # fp32 when it lands in .grad.  Halves the store of the step's dominant kernel and the optimiser's gradient read.
-        self.matrix_grads_bf16 = bool(overwrite_matrices and getattr(self, "wgrad_bf16", False))
+        self.matrix_grads_bf16 = bool(overwrite_matrices and self.wgrad_bf16)
         gm = st.g16 if self.matrix_grads_bf16 else g32
 
         # head: dlogits (fp32) -> bf16 for the MFMA path

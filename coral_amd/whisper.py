@@ -27,6 +27,7 @@ import torch
 
 from . import ops
 from .blocks import CrossAttnBlock, FFNBlock, SelfAttnBlock, zeros_on
+from .engine import Engine
 from .ops import EPI_GELU, EPI_GELU_RESIDUAL
 from .wav2vec2 import ParamStore, _r8
 from .whisper_decode import WhisperDecoding, check_beam_arguments  # noqa: F401  (check_beam_arguments: imported from here)
@@ -157,7 +158,7 @@ def sinusoid_positions(length: int, channels: int, max_timescale: float = 10000.
     return torch.cat([t.sin(), t.cos()], dim=1)
 
 
-class WhisperEngine(WhisperDecoding):
+class WhisperEngine(WhisperDecoding, Engine):
     """Forward paths of WhisperForConditionalGeneration as sequences of HIP kernels (generation: WhisperDecoding)."""
 
     def __init__(self, shape: WhisperShape, device="cuda:0"):
@@ -192,19 +193,7 @@ class WhisperEngine(WhisperDecoding):
         self._enc_ws = {}
         self._dec_ws = {}
 
-    # The trainer may still be updating parameter buckets on its optimiser stream (trainer.py); every
-    # path that reads weights waits for the bucket events first.
-    weights_ready: dict | None = None
-
-    def _await(self, bucket: str):
-        ev = self.weights_ready.get(bucket) if self.weights_ready else None
-        if ev is not None:
-            torch.cuda.current_stream().wait_event(ev)
-
-    def _await_all(self):
-        if self.weights_ready:
-            for ev in self.weights_ready.values():
-                torch.cuda.current_stream().wait_event(ev)
+    # (Engine.weights_ready: every path that reads weights waits for the trainer's bucket events first)
 
     # ---- parameters ------------------------------------------------------------------------
     def exported_names(self):

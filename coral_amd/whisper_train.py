@@ -18,7 +18,7 @@ import torch
 
 from . import ops
 from .staging import PinnedStager
-from .blocks import Scratch, _z, encoder_backward, norm_plan, wgrad_stream, zeros_on
+from .blocks import Scratch, _z, encoder_backward, wgrad_stream, zeros_on
 from .ops import MNMAJOR
 from .wav2vec2 import _r8
 from .whisper import WhisperEngine, WhisperShape, shift_tokens_right
@@ -42,7 +42,6 @@ class WhisperTrainEngine(WhisperEngine):
         self.freeze_base = freeze_base
         self.activation_dropout = activation_dropout
         self.training = True
-        self.step_seed = 0
         self._tw = None
         self._tw_key = None
 
@@ -132,6 +131,8 @@ class WhisperTrainEngine(WhisperEngine):
                               f8["scale"][i:i + 1], f8["amax"][i * S:]))
             ops.fp8_refresh_group(tasks)
 
+    bucket_copies = True  # (the e4m3 copies, once enable_fp8_forward has made them)
+
     def refresh_bucket(self, name: str):
         """Trainer hook: bucket `name` has just been updated (on the trainer's optimiser stream).  The first bucket of a
         step turns the amax words of the previous step into this step's scales."""
@@ -205,7 +206,7 @@ class WhisperTrainEngine(WhisperEngine):
             # everything except the encoder AND decoder layers' weight matrices (each gets exactly one weight gradient per
             # backward, which overwrites in the step's first micro-batch: at whisper-medium the decoder's 1.6 GB were
             # cleared here and then read back by the accumulating epilogues), over a cached range table
-            if getattr(self, "_small_ranges", None) is None:
+            if self._small_ranges is None:
                 rs, pos = [], 0
                 spans = [self._enc_matrix_range(l) for l in range(Le)] + [self._dec_matrix_range(l) for l in range(self.s.decoder_layers)]
                 for lo, hi in sorted(spans):
@@ -214,27 +215,14 @@ class WhisperTrainEngine(WhisperEngine):
                 rs.append((pos, st.numel - pos))
                 self._small_ranges = tuple(r for r in rs if r[1] > 0)
             ops.clear_ranges(st.g32, self._small_ranges)
-        plan = getattr(self, "_norm_plan", None)
-        if plan is not None:
-            ops.clear_f32(plan["slots"], plan["nslots"])
+        if self._norm_plan is not None:
+            ops.clear_f32(self._norm_plan["slots"], self._norm_plan["nslots"])
 
-    def norm_plan(self):
-        """Squared gradient norm without a pass over the encoder layers' weight matrices (blocks.norm_plan)."""
-        if self.freeze_base:
-            return None
-        if getattr(self, "_norm_plan", None) is None:
-            self._norm_plan = norm_plan(self.store, [(l, *m) for l in range(self.s.encoder_layers)
-                                                     for m in self._enc_matrices(l)], self.device)
-        return self._norm_plan
+    def norm_matrices(self):
+        """The encoder layers' weight matrices: the gradient norm needs no pass over them."""
+        return [(l, *m) for l in range(self.s.encoder_layers) for m in self._enc_matrices(l)]
 
-    def train(self, mode: bool = True):
-        self.training = mode
-        return self
-
-    def eval(self):
-        return self.train(False)
-
-    def refresh_derived(self):
+    def refresh_derived(self, part: str | None = None):
         """conv stem weights are consumed in the reordered [Co][k][Ci] layout."""
         s, st = self.s, self.store
         ops.conv_weight_reorder(st.p32, self.conv1_wr, s.d_model, s.num_mel_bins, 3, w_off=st.off("model.encoder.conv1.weight"))
@@ -496,7 +484,7 @@ class WhisperTrainEngine(WhisperEngine):
         plan = self.norm_plan()
         # encoder weight matrices: accumulate, or overwrite in a step's first micro-batch and then, when the trainer asked
         # for it, keep in bf16 - the dtype the reference's autocast computes them in (wav2vec2.py backward; NOTEBOOK R5.10)
-        self.matrix_grads_bf16 = bool(overwrite_matrices and getattr(self, "wgrad_bf16", False) and plan is not None)
+        self.matrix_grads_bf16 = bool(overwrite_matrices and self.wgrad_bf16 and plan is not None)
         cur, _, other = encoder_backward(
             self.enc_blocks, w["enc_sv"], sv["ek"], B, T, ring, (sc_e, w["sc_e2"]), (w["bias_ws"], w["bias_ws2"]),
             w["ln_part_e"], gm=st.g16 if self.matrix_grads_bf16 else g32, acc=not overwrite_matrices, plan=plan,

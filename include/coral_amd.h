@@ -907,7 +907,7 @@ int ca_comm_unique_id(void* id128_h);
 int ca_comm_init(CaComm** ctx, const void* id128_h, int32_t rank, int32_t world);
 int ca_comm_destroy(CaComm* ctx); /* waits for the context's stream, then frees communicator, stream and context */
 int ca_comm_abort(CaComm* ctx);   /* the same WITHOUT waiting (ncclCommAbort): for a context whose peers never joined a
-                                   * collective - the rendezvous fallback of the host side (coral_amd/trainer.py) */
+                                   * collective - the rendezvous fallback of the host side (coral_amd/exchange.py) */
 void* ca_comm_stream(CaComm* ctx); /* the context's hipStream_t */
 int ca_comm_rank(CaComm* ctx);
 int ca_comm_world(CaComm* ctx);

@@ -21,6 +21,7 @@ def run(forced, wire, steps, zero=0, clip=1e9):
     the 4.8 M bf16 copies then round the other way, and two steps later nothing is bit-identical any more."""
     import dp_worker
 
+    from coral_amd.exchange import collectives_selfcheck
     from coral_amd.trainer import DataParallelTrainer
 
     os.environ["CA_DP_FORCE"] = "1" if forced else "0"
@@ -34,7 +35,7 @@ def run(forced, wire, steps, zero=0, clip=1e9):
     # RCCL ranks exchange through the C ABI's ca_* collectives (include/coral_amd.h), CA_COMM_CAPI=0 = torch.distributed's
     assert (tr.sync.capi is not None) == (forced and os.environ.get("CA_COMM_CAPI", "1") != "0")
     if zero and forced:
-        assert tr._collectives_selfcheck(eng.store.device, None, tr.sync.capi)
+        assert collectives_selfcheck(eng.store.device, None, tr.sync.capi)
     mb = shard([0, 1, 2, 3])
     losses, norms = [], []
     for _ in range(steps):

@@ -19,7 +19,8 @@ def _free_port():
 def _worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     torch.distributed.init_process_group("gloo", rank=rank, world_size=world)
-    from coral_amd.trainer import GradSync, shard_indices
+    from coral_amd.exchange import GradSync
+    from coral_amd.trainer import shard_indices
 
     buckets = {"front": [0, 40], "layer0": [40, 104], "layer1": [104, 168], "head": [168, 200]}
     g = torch.arange(200, dtype=torch.float32) * (rank + 1)

@@ -34,6 +34,7 @@
 // 1 KiB) by LDS-DMA, issued as far ahead as the ring holds (about one layer): piece = 4 columns x 128 k, 256 contiguous
 // bytes per column, chunk positions XOR-ed so that the MFMA fragment reads (ds_read_b128) hit 16 distinct bank slots.
 #include "common.h"
+#include "attn_plan.h"
 #include <type_traits>
 
 typedef __attribute__((address_space(3))) void* dk_lptr_t;
@@ -1380,12 +1381,9 @@ extern "C" int ca_whisper_decode_token(const CaDecodeDesc* desc, void* stream) {
   DecArgs a;
   a.layers = c.layers; a.n_layers = c.n_layers; a.B = c.B; a.d = c.d; a.f = c.f; a.H = c.H; a.Te = c.Te; a.Lmax = c.max_len;
   a.V = c.V;
-  // key split of the cross-attention: ca_attn_fwd's rule (smallq_split), so the merge order - and the bits - are its
+  // key split of the cross-attention: ca_attn_fwd's rule (attn_plan_smallq), so the merge order - and the bits - are its
   a.split.ns = 1; a.split.tail_start = c.B * c.H; a.split.ns_tail = 1;
-  if (c.Te >= 1024) {
-    static const int cap = [] { const char* e = getenv("CA_ATTN_SPLIT"); return e ? atoi(e) : CA_ATTN_SPLIT_MAX; }();
-    a.split = ca_attn_key_split(c.B * c.H, G, cap);
-  }
+  if (c.Te >= ATTN_SPLIT_MIN_KEYS) a.split = ca_attn_key_split(c.B * c.H, G, attn_knobs().split, attn_knobs().split_tail);
   a.embed = (const unsigned short*)c.embed; a.pos_tab = (const unsigned short*)c.embed_pos;
   a.lnf_g = c.lnf_g; a.lnf_b = c.lnf_b; a.eps = c.eps; a.scale = 0.125f;  // head_dim 64
   a.logits = c.logits; a.ld_logits = c.ld_logits; a.suppress = c.suppress; a.out = c.out; a.done = c.done; a.ids = c.ids;

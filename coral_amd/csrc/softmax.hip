@@ -1,5 +1,5 @@
 // Softmax over vocabulary rows: cross-entropy (Whisper LM loss) and masked argmax (greedy generation).
-// (The attention softmax lives inside the fused attention kernels, attention.hip.)
+// (The attention softmax lives inside the fused attention kernels, attn_fwd.hip / attn_bwd.hip / attn_decode.hip.)
 #include "common.h"
 
 #define NEG_INF (-__builtin_inff())

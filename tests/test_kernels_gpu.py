@@ -463,10 +463,15 @@ def test_misc_reorders(ops):
                                                     (128, 1, 200, 200, True, True), (64, 3, 130, 333, False, True),
                                                     (64, 2, 300, 300, True, False), (120, 2, 257, 129, False, False)])
 def test_fused_attention_fwd_bwd(ops, hd, H, Tq, Tk, causal, pad):
+    _check_attention_fwd_bwd(ops, 2, hd, H, Tq, Tk, causal, pad)
+
+
+def _check_attention_fwd_bwd(ops, B, hd, H, Tq, Tk, causal, pad, dropout_p=0.0, dropout_seed=0):
     """ca_attn_fwd / ca_attn_bwd against an fp32 torch statement of softmax(scale QK^T + masks) V and
     its autograd gradients; q,k,v live in one fused [B*T, 3d] buffer like the engine's (self-attention)
-    or in separate buffers (cross-attention shapes)."""
-    B, d = 2, H * hd
+    or in separate buffers (cross-attention shapes).  With dropout the kernels' keep decisions, restated in NumPy
+    (_keep_mask_np), scale the reference's probabilities."""
+    d = H * hd
     g = torch.Generator().manual_seed(hd + Tq + Tk)
     scale = hd ** -0.5
     fused = Tq == Tk
@@ -475,7 +480,7 @@ def test_fused_attention_fwd_bwd(ops, hd, H, Tq, Tk, causal, pad):
         q, k, v = qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:]
     else:
         q, k, v = bf(torch.randn(B, Tq, d, generator=g)), bf(torch.randn(B, Tk, d, generator=g)), bf(torch.randn(B, Tk, d, generator=g))
-    klen = torch.tensor([Tk, max(1, Tk * 3 // 5)], dtype=torch.int32) if pad else None
+    klen = torch.tensor(([Tk, max(1, Tk * 3 // 5)] * B)[:B], dtype=torch.int32) if pad else None
     dO = bf(torch.randn(B, Tq, d, generator=g))
 
     def heads(x, T):
@@ -489,7 +494,13 @@ def test_fused_attention_fwd_bwd(ops, hd, H, Tq, Tk, causal, pad):
     if causal:
         mask = mask & (torch.arange(Tk)[None, None, None, :] <= torch.arange(Tq)[None, None, :, None])
     s = s.masked_fill(~mask, float("-inf"))
-    o_ref = torch.softmax(s, -1) @ vr
+    probs = torch.softmax(s, -1)
+    if dropout_p:
+        from test_whisper_gpu import _keep_mask_np
+
+        keep = _keep_mask_np(dropout_seed, B * H * Tq, Tk, dropout_p).reshape(B, H, Tq, Tk)
+        probs = probs * (torch.from_numpy(keep.astype("float32")) / (1.0 - dropout_p))
+    o_ref = probs @ vr
     o_ref.backward(heads(dO, Tq))
     o_ref = o_ref.detach().transpose(1, 2).reshape(B, Tq, d)
 
@@ -516,7 +527,7 @@ def test_fused_attention_fwd_bwd(ops, hd, H, Tq, Tk, causal, pad):
         doffs = {}
         dlds = dict(lddq=d, lddk=d, lddv=d, sdqb=Tq * d, sdkb=Tk * d, sdvb=Tk * d)
     common = dict(B=B, H=H, Tq=Tq, Tk=Tk, hd=hd, Tqp=Tqp, scale=scale, ldo=d, sob=Tq * d, klen=kd, causal=causal,
-                  **lds, **offs)
+                  dropout_p=dropout_p, dropout_seed=dropout_seed, **lds, **offs)
     ops.attn_fwd(Qd, Kd, Vd, O, lse, **common)
     torch.cuda.synchronize()
     assert (O.float().cpu() - o_ref).abs().max() < 2e-2
@@ -1038,3 +1049,86 @@ def test_gemm_automatic_choice_fires_the_planned_kernel(ops, row):
     bound = 2e-3 * max(1.0, float(ref.abs().max())) if skinny else 1e-3 * (K ** 0.5)
     print(f"plan row M {M} N {N} K {K} family {row['family']}: variant {fired}, max |err| {err:.3e}, bound {bound:.3e}")
     assert err <= bound, (err, bound)
+
+
+_ATTN_INST = ("kernel", "hdpv", "drop", "wpe", "dt", "qp", "ks")
+
+
+def _attn_plan_rows_one_per_instantiation():
+    """From tests/golden/attn_plan.json: for every attention instantiation that default knobs on the whole 256-CU chip
+    reach (kernel, head-dim image, dropout, workgroups per CU; the single-query kernel's ring depth, query projection
+    and key_slot table), the smallest problem (B H Tq Tk) that the rule sends there - without packed rows, O8 or a split
+    workspace, which no instantiation depends on; two clips and at least 40 queries for the tiled kernels."""
+    import json
+    from pathlib import Path
+
+    t = json.loads((Path(__file__).parent / "golden" / "attn_plan.json").read_text())
+    c = {k: i for i, k in enumerate(t["columns"])}
+    default = dict(wide=1, wpe3=1, dq_wpe3=1, dkv_wide=1, dkv_wpe3=0, smallq_2percu=-1, split=4, split_tail=1, device_cus=256,
+                   row_off=0, O8=0, ws=0, error=0)
+    best = {}
+    for r in t["rows"]:
+        if any(r[c[k]] != v for k, v in default.items()):
+            continue
+        row = {k: r[i] for k, i in c.items()}
+        if row["kernel0"] != 3 and (row["B"] != 2 or row["Tq"] < 40):  # (the table also holds one-element problems)
+            continue
+        size = row["B"] * row["H"] * row["Tq"] * row["Tk"]
+        for slot in range(3):
+            inst = tuple(row[f"{k}{slot}"] for k in _ATTN_INST)
+            if inst[0] and (inst not in best or size < best[inst][0]):
+                best[inst] = (size, dict(row, inst=inst))
+    # 4 + 4 forward, 6 single-query, prep, 4 + 2 dK|dV, 4 + 4 dQ (the two- / three-per-CU twins behind knobs are not default)
+    assert len(best) == 29 and {k[0] for k in best} == set(range(1, 9)), sorted(best)
+    return [best[k][1] for k in sorted(best)]
+
+
+@pytest.mark.parametrize("row", _attn_plan_rows_one_per_instantiation(),
+                         ids=lambda r: "k{}_hdpv{}_drop{}_wpe{}_dt{}_qp{}_ks{}".format(*r["inst"]))
+def test_attention_every_planned_instantiation_computes_attention(ops, row):
+    """One launch per attention instantiation at the smallest shape of the plan table that reaches it.  Forward,
+    dQ and dK|dV kernels: ca_attn_fwd + ca_attn_bwd at that shape against the fp32 torch statement with
+    test_fused_attention_fwd_bwd's bounds, dropout through the restated keep mask.  Single-query kernels: against fp32
+    torch as test_decode_attention_with_the_keys_dealt_to_several_workgroups does (2e-2), the key_slot form with the
+    keys gathered by the table, the query-projection form bit-identical to LayerNorm + GEMM + ca_attn_fwd."""
+    assert torch.cuda.get_device_properties(0).multi_processor_count == 256, "the table's default rows are for a 256-CU device"
+    B, H, Tq, Tk, hd = (row[k] for k in ("B", "H", "Tq", "Tk", "hd"))
+    if row["inst"][0] != 3:
+        _check_attention_fwd_bwd(ops, B, hd, H, Tq, Tk, bool(row["causal"]), bool(row["klen"]),
+                                 dropout_p=0.1 if row["drop"] else 0.0, dropout_seed=0x1234567 + Tq)
+        return
+    d = H * hd
+    g = torch.Generator(device=DEV).manual_seed(B * 1000 + Tk)
+    kv = torch.randn(B, Tk, 2 * d, device=DEV, generator=g).to(torch.bfloat16)
+    q = torch.randn(B, Tq, d, device=DEV, generator=g).to(torch.bfloat16)
+    kl = torch.tensor(([Tk, max(1, Tk - 37), 1, Tk // 2] * B)[:B], dtype=torch.int32, device=DEV) if row["klen"] else None
+    slot = torch.randint(0, B, (B, Tk), device=DEV, generator=g).to(torch.int32) if row["key_slot"] else None
+    akw = dict(B=B, H=H, Tk=Tk, hd=hd, scale=hd ** -0.5, ldk=2 * d, ldv=2 * d, ldo=d, skb=Tk * 2 * d, svb=Tk * 2 * d, k_off=0,
+               v_off=d, klen=kl)
+    Tqp = 32
+    lse = torch.zeros(B * H * Tqp, device=DEV)
+    if row["api"] == 1:  # ca_decode_attn_qproj: the query is LayerNorm(x) Wq^T + bq
+        x = torch.randn(B, d, device=DEV, generator=g).to(torch.bfloat16)
+        gamma, beta = 1.0 + 0.1 * torch.randn(d, device=DEV, generator=g), 0.1 * torch.randn(d, device=DEV, generator=g)
+        W = (0.05 * torch.randn(d, d, device=DEV, generator=g)).to(torch.bfloat16)
+        bias = 0.1 * torch.randn(d, device=DEV, generator=g)
+        xn, q = torch.empty_like(x), torch.empty_like(x)
+        ops.layernorm_fwd(x, gamma, beta, xn, None, B, d, 1e-5)
+        ops.gemm(xn, W, q, M=B, N=d, K=d, lda=d, ldb=d, ldc=d, bias=bias)
+        q = q.view(B, 1, d)
+    got = torch.zeros(B, Tq, d, dtype=torch.bfloat16, device=DEV)
+    ops.attn_fwd(q, kv, kv, got, lse, Tq=Tq, Tqp=Tqp, ldq=d, sqb=Tq * d, sob=Tq * d, key_slot=slot, **akw)
+    if row["api"] == 1:
+        fused = torch.ones(B, Tq, d, dtype=torch.bfloat16, device=DEV)
+        ops.decode_attn_qproj(x, gamma, beta, W, bias, kv, kv, fused, d_model=d, eps=1e-5, ldx=d, ldw=d, sob=d, **akw)
+        torch.cuda.synchronize()
+        assert torch.equal(fused, got)
+    kve = kv if slot is None else kv[slot.long(), torch.arange(Tk, device=DEV)[None, :]]  # key t of clip b from row slot[b, t]
+    K, V = kve[..., :d].float().view(B, Tk, H, hd).transpose(1, 2), kve[..., d:].float().view(B, Tk, H, hd).transpose(1, 2)
+    sc = (q.float().view(B, Tq, H, hd).transpose(1, 2) @ K.transpose(-1, -2)) * hd ** -0.5
+    if kl is not None:
+        sc = sc.masked_fill(torch.arange(Tk, device=DEV)[None, None, None, :] >= kl[:, None, None, None], float("-inf"))
+    ref = (torch.softmax(sc, -1) @ V).transpose(1, 2).reshape(B, Tq, d)
+    err = float((got.float() - ref).abs().max())
+    print(f"single-query instantiation {row['inst']} B {B} H {H} Tq {Tq} Tk {Tk} hd {hd}: max |err| {err:.3e}")
+    assert torch.isfinite(got.float()).all() and float(got.float().abs().sum()) > 0 and err < 2e-2

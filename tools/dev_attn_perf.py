@@ -1,5 +1,5 @@
 """Fused-attention kernel times at the models' shapes (tuning aid):  python tools/dev_attn_perf.py
-CA_ATTN_WIDE_MIN=100000 selects the 64-query workgroups everywhere (A/B against the 128-query ones)."""
+CA_ATTN_WIDE=0 selects the 64-query workgroups everywhere (A/B against the 128-query ones)."""
 import sys
 from pathlib import Path
 

@@ -23,21 +23,24 @@ logger = logging.getLogger(__package__)
 
 
 def transcribe(model, processor, arrays: list, batch_size: int = 16, chunk_length_s: float = 0, stride_length_s=None,
-               return_timestamps=None):
+               return_timestamps=None, timestamp_source: str = "emission"):
     """ASR-pipeline equivalent ($TF/pipelines/automatic_speech_recognition.py:345,569-575,679):
     feature-extract, forward, argmax over all frames, CTC collapse, decode.  -> list of texts.
     chunk_length_s > 0: overlapping chunks with the pipeline's `chunk_length_s` / `stride_length_s` semantics
     (coral_amd/longform.py); 0: every clip whole.  return_timestamps="char" | "word": a list of {"text", "chunks":
-    [{"text", "timestamp": (start_s, stop_s)}]} instead (greedy decoding only).  A whole clip of more than 4096 frames
-    (81.9 s), or one decoded with timestamps, is collapsed by `ca_ctc_collapse_offsets`."""
-    from .longform import check_timestamp_mode, collapse_rows, decode_rows, transcribe_long
+    [{"text", "timestamp": (start_s, stop_s)}]} instead (greedy decoding only, unless timestamp_source="alignment").
+    A whole clip of more than 4096 frames (81.9 s), or one decoded with timestamps, is collapsed by
+    `ca_ctc_collapse_offsets`.  timestamp_source="alignment": the times come from the CTC forced alignment of the decoded
+    ids to the same logits (`ca_ctc_align`) - with the greedy decoder and with the LM-fused beam search alike."""
+    from .longform import align_rows, check_timestamp_mode, collapse_rows, decode_rows, transcribe_long
 
     with_lm = getattr(processor, "lm", None) is not None
-    check_timestamp_mode(return_timestamps, with_lm)
+    check_timestamp_mode(return_timestamps, with_lm, timestamp_source)
     if chunk_length_s is not None and chunk_length_s < 0:
         raise ValueError(f"chunk_length_s must be 0 (whole clips) or positive, got {chunk_length_s}")
     if chunk_length_s:
-        res = transcribe_long(model, processor, arrays, chunk_length_s, stride_length_s, batch_size, return_timestamps)
+        res = transcribe_long(model, processor, arrays, chunk_length_s, stride_length_s, batch_size, return_timestamps,
+                              timestamp_source)
         return res if return_timestamps is not None else [r["text"] for r in res]
     model.eval()
     out = []
@@ -51,6 +54,10 @@ def transcribe(model, processor, arrays: list, batch_size: int = 16, chunk_lengt
         if with_lm:  # Wav2Vec2ProcessorWithLM: LM-fused beam search on the GPU
             ids, _ = eng.beam_decode(processor.device_tables(eng.device), tokenizer=processor.tokenizer,
                                      **processor.decoder_params)
+            if return_timestamps is not None:  # (timestamp_source="alignment": the check above refuses the other)
+                out += decode_rows(align_rows(eng, ids), processor.tokenizer, return_timestamps,
+                                   math.prod(eng.s.conv_stride), processor.feature_extractor.sampling_rate)
+                continue
         elif T > 4096 or return_timestamps is not None:
             # every frame of the padded batch, as the greedy kernel below decodes them: identity segments
             w, B, s = eng._saved["w"], eng._saved["B"], eng.s
@@ -58,8 +65,10 @@ def transcribe(model, processor, arrays: list, batch_size: int = 16, chunk_lengt
             raw = torch.empty(B, T, dtype=torch.int32, device=eng.device)
             ops.ctc_stitch(w["logits"], seg, raw, None, B, T, s.vocab_size, w["Vp"], B, T)
             sr = processor.feature_extractor.sampling_rate
-            res = decode_rows(collapse_rows(raw, None, s.pad_token_id), processor.tokenizer, return_timestamps,
-                              math.prod(s.conv_stride), sr)
+            rows = collapse_rows(raw, None, s.pad_token_id)
+            if return_timestamps is not None and timestamp_source == "alignment":
+                rows = align_rows(eng, [r[0] for r in rows])
+            res = decode_rows(rows, processor.tokenizer, return_timestamps, math.prod(s.conv_stride), sr)
             out += res if return_timestamps is not None else [r["text"] for r in res]
             continue
         else:
@@ -272,7 +281,8 @@ def evaluate(config, examples: list | None = None) -> dict:
                         for ex in synthetic_examples(processor, 2 * config.batch_size, 99, config.min_seconds_per_example,
                                                      min(3.0, config.max_seconds_per_example), config.sampling_rate)]
         preds = transcribe(model, processor, [e["audio"] for e in examples], config.batch_size,
-                           chunk_length_s=chunk_length_s, stride_length_s=config.get("stride_length_s", None))
+                           chunk_length_s=chunk_length_s, stride_length_s=config.get("stride_length_s", None),
+                           timestamp_source=config.get("timestamp_source", "emission"))
     preds = [p.lower().strip() for p in preds]
     labels = [e["text"].lower().strip() if config.lower_case else e["text"].strip() for e in examples]
     scores = dict(model_type=mtype, n=len(examples))

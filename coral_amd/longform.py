@@ -21,6 +21,7 @@ from . import ops
 
 W2V2_CONV_KERNEL, W2V2_CONV_STRIDE = (10, 3, 3, 3, 3, 2, 2), (5, 2, 2, 2, 2, 2, 2)
 TIMESTAMP_MODES = (None, "char", "word")
+TIMESTAMP_SOURCES = ("emission", "alignment")
 
 
 def conv_frames(n: int, kernels=W2V2_CONV_KERNEL, strides=W2V2_CONV_STRIDE) -> int:
@@ -122,12 +123,22 @@ def timestamp_chunks(offsets: list[dict], key: str, align_to: int, sampling_rate
                                            o["end_offset"] * align_to / sampling_rate)} for o in offsets]
 
 
-def check_timestamp_mode(return_timestamps, with_lm: bool) -> None:
+def check_timestamp_mode(return_timestamps, with_lm: bool, timestamp_source: str = "emission") -> None:
     if return_timestamps not in TIMESTAMP_MODES:
         raise ValueError(f"return_timestamps must be None, 'char' or 'word', got {return_timestamps!r}")
-    if return_timestamps is not None and with_lm:
+    if timestamp_source not in TIMESTAMP_SOURCES:
+        raise ValueError(f"timestamp_source must be 'emission' or 'alignment', got {timestamp_source!r}")
+    if return_timestamps is not None and with_lm and timestamp_source == "emission":
         raise ValueError("return_timestamps is not available with LM decoding (the beam search records no emission "
-                         "frames): load the processor with no_lm or drop return_timestamps")
+                         "frames): load the processor with no_lm, drop return_timestamps, or pass "
+                         "timestamp_source=\"alignment\" (the forced alignment of the returned string)")
+
+
+def align_rows(eng, ids: list, logits=None, in_len=None) -> list:
+    """Decoded id rows -> (ids, start, end) per row with the frames of their CTC forced alignment to the same logits
+    (`Wav2Vec2CTCEngine.align`): what `decode_rows` takes, whichever decoder produced the ids."""
+    rows, _ = eng.align(ids, in_len=in_len, logits=logits)
+    return [(list(r), start, end) for r, (start, end, _) in zip(ids, rows)]
 
 
 def collapse_rows(raw: torch.Tensor, in_len, blank: int):
@@ -221,24 +232,32 @@ def stitch_long(model, arrays: list, chunk_length_s: float, stride_length_s=None
 
 
 def transcribe_long(model, processor, arrays: list, chunk_length_s: float, stride_length_s=None, batch_size: int = 16,
-                    return_timestamps=None) -> list[dict]:
+                    return_timestamps=None, timestamp_source: str = "emission") -> list[dict]:
     """Chunked wav2vec2 transcription with the pipeline's semantics -> [{"text": str}] plus, with
     return_timestamps="char" | "word", "chunks": [{"text", "timestamp": (start_s, stop_s)}] per recording.
-    With a `Wav2Vec2ProcessorWithLM` the stitched logits go to the LM-fused beam search (no timestamps there)."""
+    With a `Wav2Vec2ProcessorWithLM` the stitched logits go to the LM-fused beam search (no emission frames there).
+    timestamp_source="alignment": the times are those of the CTC forced alignment of the decoded ids (greedy or beam) to
+    the stitched logits (`ca_ctc_align`), which serves both decoders."""
     from .wav2vec2 import Wav2Vec2CTCEngine
 
     if not isinstance(getattr(model, "engine", None), Wav2Vec2CTCEngine):
         raise ValueError("chunk_length_s > 0 is built for wav2vec2 (CTC) models only: Whisper long-form decoding is not")
     with_lm = getattr(processor, "lm", None) is not None
-    check_timestamp_mode(return_timestamps, with_lm)
+    check_timestamp_mode(return_timestamps, with_lm, timestamp_source)
     if not arrays:
         return []
     eng = model.engine
     sr = processor.feature_extractor.sampling_rate
-    st = stitch_long(model, arrays, chunk_length_s, stride_length_s, batch_size, sr, want_logits=with_lm)
+    aligned = return_timestamps is not None and timestamp_source == "alignment"
+    st = stitch_long(model, arrays, chunk_length_s, stride_length_s, batch_size, sr, want_logits=with_lm or aligned)
     if with_lm:
         ids, _ = eng.beam_decode(processor.device_tables(eng.device), tokenizer=processor.tokenizer, in_len=st["in_len"],
                                  logits=st["logits"], **processor.decoder_params)
-        return [{"text": processor.tokenizer.decode(r, group_tokens=False)} for r in ids]
-    rows = collapse_rows(st["raw"], st["in_len"], eng.s.pad_token_id)
+        if not aligned:
+            return [{"text": processor.tokenizer.decode(r, group_tokens=False)} for r in ids]
+        rows = align_rows(eng, ids, st["logits"], st["in_len"])
+    else:
+        rows = collapse_rows(st["raw"], st["in_len"], eng.s.pad_token_id)
+        if aligned:
+            rows = align_rows(eng, [r[0] for r in rows], st["logits"], st["in_len"])
     return decode_rows(rows, processor.tokenizer, return_timestamps, st["align_to"], sr)

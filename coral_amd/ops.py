@@ -578,6 +578,33 @@ def ctc_beam_decode(logits, in_len, ids_out, out_len, score_out, ws, B, T, V, ld
     check(lib().ca_ctc_beam_decode(C.byref(d), _stream()), "ca_ctc_beam_decode")
 
 
+def ctc_align_workspace_bytes(B, T, Lmax):
+    return lib().ca_ctc_align_workspace_bytes(B, T, Lmax)
+
+
+def ctc_align(logits, in_len, labels, lab_len, start, end, tok_score, score, ws, B, T, V, ldv, Lmax, blank):
+    """CTC forced alignment (ca_ctc_align): the Viterbi alignment of labels int32 [B, Lmax] (lab_len int32 [B] of them per
+    row) to logits fp32 [B, T, ldv].  The label values are checked here, on the host, where they start: `labels` and
+    `lab_len` are host tensors (or lists) and are copied to the logits' device; every used label must lie in [0, V) and
+    differ from `blank`."""
+    labels = torch.as_tensor(labels, dtype=torch.int32).reshape(B, Lmax)
+    lab_len = torch.as_tensor(lab_len, dtype=torch.int32).reshape(B)
+    if labels.is_cuda or lab_len.is_cuda:
+        raise ValueError("ctc_align: labels and lab_len are host tensors (their values are checked on the host)")
+    if Lmax > _lib.CTC_ALIGN_MAX_LABELS:
+        raise ValueError(f"ctc_align: {Lmax} labels per row, the limit is {_lib.CTC_ALIGN_MAX_LABELS}")
+    if B and (int(lab_len.min()) < 0 or int(lab_len.max()) > Lmax):
+        raise ValueError(f"ctc_align: lab_len must lie in [0, Lmax = {Lmax}]")
+    used = labels[torch.arange(Lmax)[None, :] < lab_len[:, None]]
+    if used.numel() and (int(used.min()) < 0 or int(used.max()) >= V or bool((used == blank).any())):
+        raise ValueError(f"ctc_align: labels must lie in [0, {V}) and differ from the blank id {blank}")
+    dev = logits.device
+    lab_d, len_d = labels.contiguous().to(dev), lab_len.to(dev)
+    check(lib().ca_ctc_align(_p(logits), ldv, _p(in_len), _p(lab_d), _p(len_d), _p(start), _p(end), _p(tok_score),
+                             _p(score), _p(ws), ws.numel() * _ELT[ws.dtype], B, T, V, Lmax, blank, _stream()),
+          "ca_ctc_align")
+
+
 def mask_frames(h, tmask, fmask, embed, flen, B, T, Cn):
     check(lib().ca_mask_frames(_p(h), _p(tmask), _p(fmask), _p(embed), _p(flen), B, T, Cn,
                                _stream()), "ca_mask_frames")

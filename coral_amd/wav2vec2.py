@@ -924,3 +924,45 @@ class Wav2Vec2CTCEngine(Engine):
                             beam_width=beam_width, **p)
         ids_c, olen_c = ids.cpu(), olen.cpu()
         return [ids_c[b, :int(olen_c[b])].tolist() for b in range(B)], score
+
+    def align(self, labels, in_len=None, logits=None):
+        """CTC forced alignment (ca_ctc_align) of one id list per row to the logits of the last forward, or to
+        `logits`, a contiguous fp32 device tensor [B, T, ld >= V] (the stitched rows of coral_amd/longform.py).  The ids
+        lie in [0, V) and differ from the blank (= pad) id; at most CA_CTC_ALIGN_MAX_LABELS of them per row.
+        -> (rows, score): per row the host lists (start, end, tok_score) - a token's first frame on the most probable
+        alignment, the first frame behind its last one, the mean log-probability of its frames - and the alignments'
+        log-probabilities as a host list; a row that has no alignment has score -inf and start = end = -1.  One
+        device-to-host copy."""
+        V = self.s.vocab_size
+        dev = self.device
+        if logits is None:
+            sv = self._saved
+            w = sv["w"]
+            B, T, Vp = sv["B"], w["T"], w["Vp"]
+            logits = w["logits"]
+        else:
+            if (logits.dim() != 3 or logits.dtype != torch.float32 or not logits.is_contiguous() or logits.shape[2] < V
+                    or not logits.is_cuda):
+                raise ValueError("align: logits must be a contiguous fp32 [B, T, ld >= V] tensor on the engine's device")
+            B, T, Vp = logits.shape
+        labels = [list(map(int, r)) for r in labels]
+        if len(labels) != B:
+            raise ValueError(f"align: {len(labels)} label rows for {B} rows of logits")
+        Lmax = max([len(r) for r in labels] + [1])
+        lab = torch.zeros(B, Lmax, dtype=torch.int32)
+        for b, r in enumerate(labels):
+            lab[b, :len(r)] = torch.tensor(r, dtype=torch.int32)
+        lab_len = torch.tensor([len(r) for r in labels], dtype=torch.int32)
+        # start | end | tok_score bits | score bits in one int32 buffer: one copy to the host
+        out = torch.empty(3 * B * Lmax + B, dtype=torch.int32, device=dev)
+        start, end = out[:B * Lmax].view(B, Lmax), out[B * Lmax:2 * B * Lmax].view(B, Lmax)
+        tok = out[2 * B * Lmax:3 * B * Lmax].view(torch.float32).view(B, Lmax)
+        score = out[3 * B * Lmax:].view(torch.float32)
+        ws = torch.empty(max(1, ops.ctc_align_workspace_bytes(B, T, Lmax)), dtype=torch.uint8, device=dev)
+        ops.ctc_align(logits, in_len, lab, lab_len, start, end, tok, score, ws, B, T, V, Vp, Lmax, self.s.pad_token_id)
+        host = out.cpu()
+        h = host[:2 * B * Lmax].view(2, B, Lmax)
+        ht = host[2 * B * Lmax:3 * B * Lmax].view(torch.float32).view(B, Lmax)
+        rows = [(h[0, b, :len(r)].tolist(), h[1, b, :len(r)].tolist(), ht[b, :len(r)].tolist())
+                for b, r in enumerate(labels)]
+        return rows, host[3 * B * Lmax:].view(torch.float32).tolist()

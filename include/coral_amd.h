@@ -590,6 +590,34 @@ int64_t ca_ctc_beam_workspace_bytes(int32_t B, int32_t T, int32_t V, int32_t bea
 int ca_ctc_beam_decode(const CaCtcBeamDesc* desc, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * CTC forced alignment (coral_amd/ctc_align.py, Wav2Vec2CTCEngine.align; word times under LM decoding, where the
+ * transformers pipeline offers return_timestamps="word" only, $TF/pipelines/automatic_speech_recognition.py): the
+ * single most probable alignment of a label string to the frames, Viterbi over the blank-interleaved states.
+ *   logits fp32 [B,T,ldv] (first V columns valid, 2 <= V <= 256; log_softmax in fp32 is taken inside); in_len int32 [B]
+ *   or NULL for T.  labels int32 [B,Lmax], lab_len int32 [B] with 0 <= lab_len <= Lmax <= CA_CTC_ALIGN_MAX_LABELS;
+ *   label values lie in [0,V) and differ from blank (the caller checks: coral_amd/ops.py does, on the host).
+ *   States s = 0..2L, l'_s = blank for even s and labels[(s-1)/2] for odd s.  v_0(0) = lp[0][blank], v_0(1) =
+ *   lp[0][l_0], every other v_0 = -inf; v_t(s) = lp[t][l'_s] + max(v_{t-1}(s), v_{t-1}(s-1), v_{t-1}(s-2)), the s-2
+ *   move only for odd s with l'_s != l'_{s-2}.  The path ends in state 2L or 2L-1 at frame in_len-1.
+ *   Tie rule: among equal predecessors the smaller move wins (stay, then s-1, then s-2); at the end a tie between
+ *   states 2L and 2L-1 takes 2L.
+ *   start / end int32 [B,Lmax]: the first frame of token i on the best path and the first frame behind its last one
+ *   (the convention of ca_ctc_collapse_offsets), -1 behind lab_len.  tok_score fp32 [B,Lmax]: the mean lp of the
+ *   token's own label over its frames (0 behind lab_len).  score fp32 [B]: the path's total log-probability;
+ *   lab_len = 0 gives the all-blank path's.  A row with no alignment (lab_len + number of adjacent equal labels >
+ *   in_len, or in_len = 0) has score = -inf, start = end = -1 and tok_score = -inf, and the call still succeeds.
+ *   Deterministic: bit-identical from run to run and independent of the row's position in the batch.
+ *   ws: ca_ctc_align_workspace_bytes(B, T, Lmax) bytes (per-frame logsumexp, then 2-bit back-pointers packed 4 states
+ *   to the byte).  No allocation, no synchronisation; bad arguments return CA_ERR_ARG with the function's name in
+ *   ca_last_error().
+ * ---------------------------------------------------------------------------------- */
+#define CA_CTC_ALIGN_MAX_LABELS 4095
+int64_t ca_ctc_align_workspace_bytes(int32_t B, int32_t T, int32_t Lmax);
+int ca_ctc_align(const float* logits, int64_t ldv, const int32_t* in_len, const int32_t* labels,
+                 const int32_t* lab_len, int32_t* start, int32_t* end, float* tok_score, float* score, void* ws,
+                 int64_t ws_bytes, int32_t B, int32_t T, int32_t V, int32_t Lmax, int32_t blank, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Small elementwise pieces of the wav2vec2 encoder.
  * ca_mask_frames: SpecAugment + padding ($TF/.../modeling_wav2vec2.py:1272-1316, 752-755):
  *   h[b,t,:] = embed where tmask[b,t]; h[b,t,c] = 0 where fmask[b,c]; h[b,t,:] = 0 for

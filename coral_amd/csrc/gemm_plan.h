@@ -1,6 +1,6 @@
-// Kernel choice and launch geometry of the GEMM family (gemm.hip), as plain C++17: which kernel a descriptor gets and
+// Kernel choice and launch geometry of the GEMM family (gemm.hip and the gemm_*.hip kernel files), as plain C++17: which kernel a descriptor gets and
 // with what grid, block and LDS size is decided here, without touching the device, so that the rule can be compiled
-// and tested by the host compiler alone (tests/test_gemm_plan_cpu.py).  gemm.hip validates, plans, launches.
+// and tested by the host compiler alone (tests/test_gemm_plan_cpu.py).  gemm.hip validates and plans; the launcher of the plan's kernel file launches.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -12,7 +12,7 @@
 #define CA_PLAN_FN inline
 #endif
 
-// tile shapes and dynamic LDS sizes of the kernels (the layouts behind the byte counts are described in gemm.hip)
+// tile shapes and dynamic LDS sizes of the kernels (the layouts behind the byte counts are described in each kernel's file)
 #define BM 128  // kernels S and M
 #define BN 128
 #define BK 64

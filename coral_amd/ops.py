@@ -272,7 +272,7 @@ def _fill(t):
     return t / (256.0 * ((t + 255) // 256))
 
 
-GROUP_MAX = 8  # problems per grouped launch (X_GROUP_MAX in gemm.hip)
+GROUP_MAX = 8  # problems per grouped launch (X_GROUP_MAX in gemm_common.h)
 
 
 _PLAN_CACHE: dict = {}

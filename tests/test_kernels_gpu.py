@@ -88,6 +88,57 @@ def test_gemm_128x128_two_waves_per_simd_kernel(ops, al, bl, M, N, K):
         ops.lib().ca_gemm_force_kernel(0)
 
 
+@pytest.mark.parametrize("force", [1, 3])
+@pytest.mark.parametrize("al,bl", [(1, 0), (0, 1), (1, 1)])
+@pytest.mark.parametrize("kseg", [24, 100])
+def test_gemm_segmented_k(ops, kseg, al, bl, force):
+    """Segmented K (a_kseg / b_kseg: row(k) = (k / kseg) * kseg_stride + (k % kseg) * ld of an MN-major operand) on the
+    two kernels that have it, S and X, forced.  The source is [nseg][kseg + 5][ld]: five gap rows of 1e4 behind every
+    segment, so a wrong hop misses every bound by orders of magnitude.  M, N ragged for both tile sizes, K = 200 with a
+    partial last K-step; kseg = 24: two or three hops inside one 64-row K-step and a partial last segment, kseg = 100:
+    K-steps with no hop and with one.  A K-major operand keeps kseg = 0.
+    (a) every bit of the fp32 output equals the same kernel's on a contiguous copy of the gathered operand (kseg = 0):
+    both instantiations feed the same values to the same MFMA chain in the same order, only the addresses differ;
+    (b) test_gemm_layouts' bound against the fp32 torch product; (c) the profiler's variant is kind * 8 + 4 + lay."""
+    M, N, K = 136, 264, 200
+    nseg, rps = -(-K // kseg), kseg + 5
+    krow = torch.arange(K)
+    src_row = (krow // kseg) * rps + krow % kseg  # row of k in the [nseg * rps][ld] source
+
+    def operand(rows, layout, seed):
+        """(device operand as passed, its contiguous twin, [rows][K] fp32 values, ld, kseg arguments)"""
+        x = bf(rnd(rows, K, seed=seed, scale=0.5))
+        if layout == 0:
+            return x.to(DEV), x.to(DEV), x.float(), K, (0, 0)
+        seg = torch.full((nseg * rps, rows), 1e4, dtype=torch.bfloat16)
+        seg[src_row] = x.t()
+        return seg.to(DEV), x.t().contiguous().to(DEV), x.float(), rows, (kseg, rps * rows)
+
+    Ad, Ac, Af, lda, (ak, aks) = operand(M, al, 1)
+    Bd, Bc, Bf, ldb, (bk, bks) = operand(N, bl, 2)
+    ref = Af @ Bf.t()
+    kw = dict(M=M, N=N, K=K, lda=lda, ldb=ldb, ldc=N, a_layout=al, b_layout=bl)
+    C = torch.zeros(M, N, dtype=torch.float32, device=DEV)
+    Cc = torch.zeros(M, N, dtype=torch.float32, device=DEV)
+    ops.lib().ca_gemm_force_kernel(force)
+    try:
+        ops.prof_begin()
+        try:
+            ops.gemm(Ad, Bd, C, a_kseg=ak, a_kseg_stride=aks, b_kseg=bk, b_kseg_stride=bks, **kw)
+        finally:
+            fired = [i for i, p in enumerate(ops.prof_end()) if p["count"]]
+        ops.gemm(Ac, Bc, Cc, **kw)
+        torch.cuda.synchronize()
+    finally:
+        ops.lib().ca_gemm_force_kernel(0)
+    err = (C.cpu() - ref).abs().max().item()
+    print(f"segmented K: kseg {kseg} lay {al}{bl} force {force}: variant {fired}, max |err| {err:.3e}, "
+          f"bits differing from the contiguous run {int((C != Cc).sum())}")
+    assert torch.equal(C, Cc)
+    assert err <= 1e-3 * (K ** 0.5), err
+    assert fired == [(0 if force == 1 else 2) * 8 + 4 + al * 2 + bl], fired
+
+
 def test_gemm_epilogues_and_batch(ops):
     M, N, K, Bt = 300, 256, 192, 3
     A, W = bf(rnd(Bt, M, K, seed=3, scale=0.5)), bf(rnd(N, K, seed=4, scale=0.2))
@@ -802,7 +853,7 @@ def test_sumsq_ranges_and_plain_sum(ops):
 
 @pytest.mark.parametrize("force", [1, 2, 3, 5])
 def test_gemm_interior_tile_epilogue_is_bit_identical_to_the_general_walk(ops, force):
-    """Interior 64 x 64 wave tiles take a specialised, predicate-free epilogue (gemm.hip, gemm_epilogue_fast); ragged
+    """Interior 64 x 64 wave tiles take a specialised, predicate-free epilogue (gemm_common.h, gemm_epilogue_fast); ragged
     ones the general walk.  Same arithmetic in the same order: with the specialised form switched off
     (ca_gemm_debug_general_epilogue) every output bit is the same - plain bf16 / bias, bias + GELU + dropout with both
     outputs, residual (+ dropout), GELU'(R) + dropout, fp32 output written and accumulated with the per-tile sums of
@@ -850,6 +901,43 @@ def test_gemm_interior_tile_epilogue_is_bit_identical_to_the_general_walk(ops, f
             for a, b in zip(got, want):
                 assert torch.equal(a, b), (force, case)
             assert float(got[0].float().abs().sum()) > 0
+    finally:
+        lib.ca_gemm_debug_general_epilogue(0)
+        lib.ca_gemm_force_kernel(0)
+
+
+@pytest.mark.parametrize("force", [1, 3])
+def test_gemm_fp8_interior_tile_epilogue_is_bit_identical_to_the_general_walk(ops, force):
+    """The same for the fp8 kernels (128 x 128 and 256 x 256, forced), whose file has its own copy of the switch
+    ca_gemm_debug_general_epilogue sets: plain and bias + GELU with both outputs, at a shape with interior and ragged
+    wave tiles for both tile sizes.  (Random e4m3 bytes below 2 in magnitude, unit scales.)"""
+    lib = ops.lib()
+    M, N, K = 300, 264, 256
+    g = torch.Generator(device=DEV).manual_seed(6)
+    sign = torch.randint(0, 2, (M + N, K), device=DEV, generator=g) * 0x80
+    AB = (torch.randint(0, 0x40, (M + N, K), device=DEV, generator=g) + sign).to(torch.uint8)
+    A8, B8 = AB[:M], AB[M:]
+    bias = torch.randn(N, device=DEV, generator=g)
+    kw = dict(M=M, N=N, K=K, lda=K, ldb=K, ldc=N, alpha=1.0 / 16)
+
+    def run(gelu):
+        out = torch.full((M, N), 0.5, dtype=torch.bfloat16, device=DEV)
+        out2 = torch.zeros(M, N, dtype=torch.bfloat16, device=DEV)
+        extra = dict(bias=bias, epilogue=ops.EPI_GELU, C2=out2, c2_off=0) if gelu else {}
+        ops.gemm_fp8(A8, B8, out, **kw, **extra)
+        torch.cuda.synchronize()
+        return out.clone(), out2.clone()
+
+    lib.ca_gemm_force_kernel(force)
+    try:
+        for gelu in (False, True):
+            lib.ca_gemm_debug_general_epilogue(1)
+            want = run(gelu)
+            lib.ca_gemm_debug_general_epilogue(0)
+            got = run(gelu)
+            for a, b in zip(got, want):
+                assert torch.equal(a, b), (force, gelu)
+            assert float(got[0].float().abs().sum()) > 0 and not bool(torch.isnan(got[0].float()).any())
     finally:
         lib.ca_gemm_debug_general_epilogue(0)
         lib.ca_gemm_force_kernel(0)

@@ -1,4 +1,4 @@
-"""Where a kernel-X workgroup's cycles go (needs the -DX_STAMPS build of gemm.hip: CORAL_AMD_LIB=coral_amd/libvariant_stamps.so)."""
+"""Where a kernel-X workgroup's cycles go (needs the -DX_STAMPS build of gemm_x.hip: CORAL_AMD_LIB=coral_amd/libvariant_stamps.so)."""
 import ctypes
 import sys
 from pathlib import Path

@@ -5,7 +5,9 @@ The three block kinds are exactly the ones of `WhisperEncoderLayer` / `WhisperDe
 residual GELU feed-forward.  The Whisper engines build their encoder and decoder layers from them (the training
 forward, `encode`, the teacher-forced `decode` and the feed-forward of the incremental decoding paths); the
 wav2vec2 engine its XLS-R encoder layers (the stable-LayerNorm layer, $TF/models/wav2vec2/modeling_wav2vec2.py:
-611-654, is the same pre-LN self-attention + feed-forward pair).
+611-654, is the same pre-LN self-attention + feed-forward pair).  What stands around the layers - the strided convs of
+both front ends, the wav2vec2 feature projection and positional conv, the final LayerNorm + output projection of both
+models - are blocks of the same kind in stem_blocks.py.
 
 Every block works on flat row-major bf16 activations [B*T, d] and a `ParamStore` (fp32 masters `p32`,
 bf16 compute copies `p16`, fp32 gradients `g32`); weight gradients are accumulated in fp32.  Workspaces come

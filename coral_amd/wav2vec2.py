@@ -13,7 +13,8 @@ HBM layout
   * activations: channels-last [B*T, C] bf16; q,k,v of a layer live in one [B*T, 3d] matrix; the encoder
     layers are blocks.SelfAttnBlock + blocks.FFNBlock (fused attention, no [T, T] matrix in HBM);
   * conv layers 1..6 and the grouped positional conv run as implicit GEMMs over overlapping-row
-    views (no im2col is ever materialised in the forward pass);
+    views (no im2col is ever materialised in the forward pass); they, the feature projection and the head are the blocks
+    of stem_blocks.py;
   * packed mode (`pack_frames`): in a training step with labels the valid frames of the batch are laid
     end to end behind the positional conv, and the encoder layers, the final LayerNorm and lm_head run on those
     Mp = sum(flen) rows - a prefix of the same [B*T, C] buffers; logits and the gradient wrt h[0] return to [B, T, *].
@@ -28,10 +29,10 @@ from dataclasses import dataclass
 import torch
 
 from . import ops
-from .blocks import FFNBlock, Scratch, SelfAttnBlock, encoder_backward, layernorm_bwd, wgrad_stream
+from .blocks import FFNBlock, Scratch, SelfAttnBlock, encoder_backward, wgrad_stream
 from .engine import Engine
 from .staging import PinnedStager
-from .ops import EPI_GELU_RESIDUAL, EPI_RESIDUAL, MNMAJOR
+from .stem_blocks import ConvFeatureEncoder, FeatureProjection, LMHead, PosConvEmbed
 
 
 @dataclass
@@ -253,10 +254,18 @@ class Wav2Vec2CTCEngine(Engine):
         if not torch.cuda.is_available():
             raise ops.CoralAmdError("Wav2Vec2CTCEngine needs a GPU: there is no CPU path")
         s = shape
-        assert s.conv_dim[0] == 512 and s.conv_kernel[0] == 10, "layer-0 kernel expects C=512,k=10"
         assert s.hidden_size % 8 == 0 and (s.hidden_size // s.num_conv_pos_embedding_groups) % 8 == 0
         assert s.head_dim % 8 == 0
         self.store = ParamStore(w2v2_param_list(s), self.device)
+        d = s.hidden_size
+        self.feature_encoder = ConvFeatureEncoder(self.store, "wav2vec2.feature_extractor.conv_layers.", s.conv_dim,
+                                                  s.conv_kernel, s.conv_stride, s.layer_norm_eps, CONV_F32)
+        self.feature_projection = FeatureProjection(self.store, "wav2vec2.feature_projection.", s.conv_dim[-1], d,
+                                                    s.layer_norm_eps)
+        self.pos_conv = PosConvEmbed(self.store, "wav2vec2.encoder.pos_conv_embed.conv.", d, s.num_conv_pos_embedding_groups,
+                                     s.num_conv_pos_embeddings)
+        self.head = LMHead(self.store, "wav2vec2.encoder.layer_norm", "lm_head.weight", "lm_head.bias", d, s.vocab_size,
+                           s.layer_norm_eps)
         self.blocks = []  # encoder layer l: (self-attention block, feed-forward block)
         for l in range(s.num_hidden_layers):
             p = f"wav2vec2.encoder.layers.{l}."
@@ -275,19 +284,7 @@ class Wav2Vec2CTCEngine(Engine):
         self._ctc_key = None
         self._stager = PinnedStager(self.device)
         self._saved = None
-        d = s.hidden_size
-        G = s.num_conv_pos_embedding_groups
-        K = s.num_conv_pos_embeddings
-        dev = self.device
-        # reordered / derived bf16 weights
-        self.conv_wr = [None] + [
-            torch.zeros(s.conv_dim[i] * s.conv_kernel[i] * s.conv_dim[i - 1], dtype=torch.bfloat16, device=dev)
-            for i in range(1, len(s.conv_dim))]
-        self.pc_wf = torch.zeros(d * K * (d // G), dtype=torch.bfloat16, device=dev)
-        self.pc_wb = torch.zeros(d * K * (d // G), dtype=torch.bfloat16, device=dev)
-        self.pc_norm = torch.zeros(K, dtype=torch.float32, device=dev)
-        self.pc_partial = torch.zeros(ops.posconv_partial_floats(K), dtype=torch.float32, device=dev)
-        self.zero_embed = torch.zeros(d, dtype=torch.bfloat16, device=dev)
+        self.zero_embed = torch.zeros(d, dtype=torch.bfloat16, device=self.device)
 
     # ---- parameters ------------------------------------------------------------------------
     def load_state_dict(self, P: dict, strict: bool = True, seed: int = 4242, init_missing: bool = True) -> dict:
@@ -424,18 +421,10 @@ class Wav2Vec2CTCEngine(Engine):
     def refresh_derived(self, part: str | None = None):
         """Weights whose compute copy is not a plain cast (after an optimiser step the flat bf16
         copy is already written by ca_adamw_step).  part: None = all, or one of `derived_parts`."""
-        s, st = self.s, self.store
         if part in (None, "conv"):
-            for i in range(1, len(s.conv_dim)):
-                ops.conv_weight_reorder(st.p32, self.conv_wr[i], s.conv_dim[i], s.conv_dim[i - 1],
-                                        s.conv_kernel[i],
-                                        w_off=st.off(f"wav2vec2.feature_extractor.conv_layers.{i}.conv.weight"))
-        if part not in (None, "posconv"):
-            return
-        d, G, K = s.hidden_size, s.num_conv_pos_embedding_groups, s.num_conv_pos_embeddings
-        pre = "wav2vec2.encoder.pos_conv_embed.conv.parametrizations.weight."
-        ops.posconv_weight(st.view(pre + "original1"), st.view(pre + "original0"), self.pc_wf, self.pc_wb,
-                           self.pc_norm, self.pc_partial, d, d // G, K)
+            self.feature_encoder.refresh()
+        if part in (None, "posconv"):
+            self.pos_conv.refresh()
 
     # ---- shapes / workspaces -------------------------------------------------------------------
     def conv_lengths(self, N: int) -> list[int]:
@@ -461,32 +450,28 @@ class Wav2Vec2CTCEngine(Engine):
         Ts = self.conv_lengths(N)
         T = Ts[-1]
         M = B * T
-        G, K = s.num_conv_pos_embedding_groups, s.num_conv_pos_embeddings
-        Cg = d // G
         bf, f32 = torch.bfloat16, torch.float32
 
         def build(z):
             # (run twice: once to measure, once to carve views out of ONE zero-filled arena - a workspace used to
             # be ~450 separate torch.zeros fills)
             w = {"B": B, "N": N, "Ts": Ts, "T": T, "M": M}
-            C0 = s.conv_dim[0]
-            cdt = f32 if CONV_F32 else bf
-            w["a"] = [z(B * Ts[i] * s.conv_dim[i], dt=cdt if i == 6 else bf) for i in range(7)]  # conv block outputs
-            w["y"] = [None] + [z(B * Ts[i] * s.conv_dim[i], dt=cdt) for i in range(1, 7)]  # pre-LN conv outputs
-            w["cstats"] = [None] + [z(B * Ts[i] * 2, dt=f32) for i in range(1, 7)]
-            w["fp_stats"] = z(M * 2, dt=f32)
-            w["xln"] = z(M * C0)
+            pf = max(
+                ops.layernorm_bwd_partial_floats(B * Ts[1], 512), ops.layernorm_bwd_partial_floats(M, d),
+                ops.colsum_partial_floats(M, max(f, 3 * d)), ops.colsum_partial_floats(B * Ts[1], 512),
+                ops.conv0_bwd_partial_floats(B, N, s.conv_dim[0], s.conv_kernel[0], s.conv_stride[0]), 4096)
+            w["partial"] = z(pf, dt=f32)
+            # the blocks' saved activations and backward scratch (stem_blocks.py, blocks.py)
+            w["fe"] = self.feature_encoder.alloc(B, Ts, z, w["partial"])
+            w["fp"] = self.feature_projection.alloc(M, z)
             w["h0"] = z(M * d)
-            w["xg"] = z(B * G * (T + K) * Cg + 8 * Cg)
-            w["pc_pre"] = z(M * d)
+            w["pc"] = self.pos_conv.alloc(B, T, z)
             w["h"] = [z(M * d) for _ in range(L + 1)]      # residual stream entering layer l (h[L] = out)
             w["hpk"] = z(M * d)                            # packed mode: the valid rows of h[0], laid end to end
             w["h1"] = [z(M * d) for _ in range(L)]         # ... between layer l's attention and feed-forward blocks
-            w["sv"] = [(sa.alloc(B, T, z), ff.alloc(M, z)) for sa, ff in self.blocks]  # the blocks' saved activations
-            w["hf"] = z(M * d)
-            w["stf"] = z(M * 2, dt=f32)
-            Vp = _r8(s.vocab_size)
-            w["Vp"] = Vp
+            w["sv"] = [(sa.alloc(B, T, z), ff.alloc(M, z)) for sa, ff in self.blocks]
+            w["head"] = self.head.alloc(M, z)
+            Vp = w["Vp"] = self.head.Vp
             w["logits"] = z(M * Vp, dt=f32)
             w["dlogits"] = z(M * Vp, dt=f32)
             w["dlogits16"] = z(M * Vp)
@@ -505,19 +490,6 @@ class Wav2Vec2CTCEngine(Engine):
             w["bias_ws"] = [z(ops.COLSUM_PARTS * (5 * d + f), dt=f32) for _ in range(2)]
             # LayerNorm-backward partials (d gamma | d beta per row block) of a layer's two norms, two layers in flight
             w["ln_partial"] = [[z(ops.layernorm_bwd_partial_floats(M, d), dt=f32) for _ in range(2)] for _ in range(2)]
-            w["dxg"] = z(B * G * (T + K) * Cg + 8 * Cg)
-            w["dwf"] = z(d * K * Cg, dt=f32)
-            nmax = max(B * Ts[i] * s.conv_kernel[i] * s.conv_dim[i - 1] for i in range(1, 7))
-            w["dcol"] = z(nmax)
-            w["dconv"] = [z(B * Ts[i] * s.conv_dim[i]) for i in range(7)]   # grads wrt conv block outputs
-            w["dy"] = z(max(B * Ts[i] * s.conv_dim[i] for i in range(1, 7)))
-            w["dwr"] = z(max(s.conv_dim[i] * s.conv_kernel[i] * s.conv_dim[i - 1] for i in range(1, 7)), dt=f32)
-            w["dwr_part"] = z(B * max(s.conv_dim[i] * s.conv_kernel[i] * s.conv_dim[i - 1] for i in range(1, 7)), dt=f32)
-            pf = max(
-                ops.layernorm_bwd_partial_floats(B * Ts[1], 512), ops.layernorm_bwd_partial_floats(M, d),
-                ops.colsum_partial_floats(M, max(f, 3 * d)), ops.colsum_partial_floats(B * Ts[1], 512),
-                ops.conv0_bwd_partial_floats(B, N, C0, s.conv_kernel[0], s.conv_stride[0]), 4096)
-            w["partial"] = z(pf, dt=f32)
             return w
 
         w = _arena_build(build, dev, bf)
@@ -553,10 +525,7 @@ class Wav2Vec2CTCEngine(Engine):
         w = self._workspace(B, N)
         d = s.hidden_size
         L = s.num_hidden_layers
-        Ts, T, M, Vp = w["Ts"], w["T"], w["M"], w["Vp"]
-        eps = s.layer_norm_eps
-        p32, p16 = st.p32, st.p16
-        o = st.off
+        T, M, Vp = w["T"], w["M"], w["Vp"]
 
         if attention_mask is not None:
             am = self._stager.to_device(attention_mask, torch.int32, "am")
@@ -586,48 +555,17 @@ class Wav2Vec2CTCEngine(Engine):
         self.last_rows, self.last_frames = Me, M
         self._await("front")
 
-        # feature encoder
-        p0 = "wav2vec2.feature_extractor.conv_layers.0."
-        ops.conv0_fwd(x, st.view(p0 + "conv.weight"), st.view(p0 + "conv.bias"),
-                      st.view(p0 + "layer_norm.weight"), st.view(p0 + "layer_norm.bias"), w["a"][0],
-                      B, N, s.conv_dim[0], s.conv_kernel[0], s.conv_stride[0], eps)
-        Lin = Ts[0]
-        for i in range(1, 7):
-            pi = f"wav2vec2.feature_extractor.conv_layers.{i}."
-            k, sd, Ci, Co = s.conv_kernel[i], s.conv_stride[i], s.conv_dim[i - 1], s.conv_dim[i]
-            ops.gemm(w["a"][i - 1], self.conv_wr[i], w["y"][i], M=Ts[i], N=Co, K=k * Ci, lda=sd * Ci,
-                     ldb=k * Ci, ldc=Co, bias=p32, bias_off=o(pi + "conv.bias"), batch2=B,
-                     sA=(0, Lin * Ci), sC=(0, Ts[i] * Co))
-            ops.layernorm_fwd(w["y"][i], st.view(pi + "layer_norm.weight"), st.view(pi + "layer_norm.bias"),
-                              w["a"][i], w["cstats"][i], B * Ts[i], Co, eps, act=1)
-            Lin = Ts[i]
-        feats = w["a"][6]
-        C6 = s.conv_dim[6]
-        # feature projection
-        fp = "wav2vec2.feature_projection."
-        ops.layernorm_fwd(feats, st.view(fp + "layer_norm.weight"), st.view(fp + "layer_norm.bias"),
-                          w["xln"], w["fp_stats"], M, C6, eps)
-        ops.gemm(w["xln"], p16, w["h0"], M=M, N=d, K=C6, lda=C6, ldb=C6, ldc=d,
-                 b_off=o(fp + "projection.weight"), bias=p32, bias_off=o(fp + "projection.bias"))
-        pf = self.dropout_site("feat_proj")
-        if pf[0] > 0:
-            ops.dropout(w["h0"], w["h0"], M * d, *pf)
+        feats = self.feature_encoder.forward(x, w["fe"], B, N)
+        self.feature_projection.forward(feats, w["h0"], w["fp"], M, self.dropout_site("feat_proj"))
         # SpecAugment + padding
         # (host-sampled masks and labels go through pinned staging: a pageable .to(device) here would stall the host
         # until the GPU had drained the previous step)
         tm = self._stager.to_device(mask_time, torch.uint8, "tm") if mask_time is not None else None
         fm = self._stager.to_device(mask_feature, torch.uint8, "fm") if mask_feature is not None else None
-        ops.mask_frames(w["h0"], tm, fm, p16[o("wav2vec2.masked_spec_embed"):], flen, B, T, d)
+        ops.mask_frames(w["h0"], tm, fm, st.p16[st.off("wav2vec2.masked_spec_embed"):], flen, B, T, d)
         # positional conv embedding: h = h0 + gelu(conv(h0) + b)
         self._await("front_posconv")
-        G, K = s.num_conv_pos_embedding_groups, s.num_conv_pos_embeddings
-        Cg = d // G
-        Tpad = T + K
-        ops.regroup_pad(w["h0"], w["xg"], B, T, G, Cg, K // 2)
-        ops.gemm(w["xg"], self.pc_wf, w["pc_pre"], C2=w["h"][0], R=w["h0"], ldr=d, M=T, N=Cg, K=K * Cg,
-                 lda=Cg, ldb=K * Cg, ldc=d, bias=p32, bias_off=o("wav2vec2.encoder.pos_conv_embed.conv.bias"),
-                 epilogue=EPI_GELU_RESIDUAL, batch1=B, batch2=G, sA=(G * Tpad * Cg, Tpad * Cg),
-                 sB=(0, Cg * K * Cg), sC=(T * d, Cg), sR=(T * d, Cg), sBias=(0, Cg))
+        self.pos_conv.forward(w["h0"], w["h"][0], w["pc"], B, T)
         pa = self.dropout_site("pos_conv")
         if pa[0] > 0:  # (hidden dropout on the sum h0 + pos_conv(h0): layer 0 and its LN backward read the dropped values)
             ops.dropout(w["h"][0], w["h"][0], M * d, *pa)
@@ -652,16 +590,11 @@ class Wav2Vec2CTCEngine(Engine):
         for l in range(L):  # dropped layers were not waited for above; the backward reads every layer's weights
             if not keep[l]:
                 self._await(f"layer{l}")
-        ops.layernorm_fwd(hs[L], st.view("wav2vec2.encoder.layer_norm.weight"),
-                          st.view("wav2vec2.encoder.layer_norm.bias"), w["hf"], w["stf"], Me, d, eps)
-        pz = self.dropout_site("final")
-        if pz[0] > 0:  # in place: lm_head and its weight gradient both read the dropped values
-            ops.dropout(w["hf"], w["hf"], Me * d, *pz)
         V = s.vocab_size
         # (packed: the Mp logit rows land in the dlogits buffer - CTC writes it only afterwards - and are scattered from
         # there into the [B, T, Vp] buffer CTC and the caller read, zeros in the padded frames)
-        ops.gemm(w["hf"], p16, w["logits"] if rows is None else w["dlogits"], M=Me, N=V, K=d, lda=d, ldb=d, ldc=Vp,
-                 b_off=o("lm_head.weight"), bias=p32, bias_off=o("lm_head.bias"))
+        self.head.forward(hs[L], w["head"], Me, logits=w["logits"] if rows is None else w["dlogits"],
+                          drop=self.dropout_site("final"))
         if rows is not None:
             ops.unpack_rows(w["dlogits"], w["logits"], rows[0], B, T, Vp)
         logits = w["logits"].view(B, T, Vp)[:, :, :V]
@@ -704,18 +637,15 @@ class Wav2Vec2CTCEngine(Engine):
         B, N = sv["B"], sv["N"]
         d = s.hidden_size
         L = s.num_hidden_layers
-        Ts, T, M, Vp = w["Ts"], w["T"], w["M"], w["Vp"]
-        V = s.vocab_size
-        p16, g32 = st.p16, st.g32
-        o = st.off
+        T, M, Vp = w["T"], w["M"], w["Vp"]
         part = w["partial"]
-        acc = True  # small tensors, front and head always accumulate (zero_grad clears them)
+        # small tensors, front and head always accumulate (zero_grad clears them)
         lacc = not overwrite_matrices  # layer weight matrices: accumulate or overwrite
         # ... and, when they are overwritten (one micro-batch per optimiser step) and the trainer asked for it, kept in
         # bf16: the reference's autocast computes a Linear's weight gradient as a bf16 matmul output and only casts it to
         # fp32 when it lands in .grad.  Halves the store of the step's dominant kernel and the optimiser's gradient read.
         self.matrix_grads_bf16 = bool(overwrite_matrices and self.wgrad_bf16)
-        gm = st.g16 if self.matrix_grads_bf16 else g32
+        gm = st.g16 if self.matrix_grads_bf16 else st.g32
 
         # head: dlogits (fp32) -> bf16 for the MFMA path
         dl = w["dlogits"]
@@ -731,18 +661,7 @@ class Wav2Vec2CTCEngine(Engine):
         if rows is not None:
             ops.pack_rows(d16, w["dlogits16p"], rows[0], B, T, Vp)
             d16 = w["dlogits16p"]
-        ops.gemm(d16, w["hf"], g32, M=V, N=d, K=Me, a_layout=MNMAJOR, lda=Vp, b_layout=MNMAJOR, ldb=d,
-                 ldc=d, c_off=o("lm_head.weight"), out_f32=True, accumulate=acc)
-        ops.colsum(d16, Vp, Me, Vp, g32, part, out_off=o("lm_head.bias"))
-        if self.freeze_base:
-            done("head")
-            return
-        ops.gemm(d16, p16, w["dA"], M=Me, N=d, K=V, lda=Vp, b_layout=MNMAJOR, ldb=d, ldc=d,
-                 b_off=o("lm_head.weight"))
         tr = sv["training"]
-        pz = self.dropout_site("final", training=tr)
-        if pz[0] > 0:
-            ops.dropout(w["dA"], w["dA"], Me * d, *pz)
 
         def branch_site(j):
             """(p, seed) of the hidden dropout whose output the residual stream h[j] carries: the FFN-output site of the
@@ -758,10 +677,11 @@ class Wav2Vec2CTCEngine(Engine):
         # ring[0]: the gradient wrt the residual stream leaving layer L-1; mring[0]: dropout(ring[0]) with the mask of the
         # hidden-dropout site whose output that stream carries - the gradient of that site's branch
         drop = branch_site(L)
-        layernorm_bwd(w["dA"], hs[L], st.view("wav2vec2.encoder.layer_norm.weight"), w["stf"], None, ring[0],
-                      st.view("wav2vec2.encoder.layer_norm.weight", "g32"), st.view("wav2vec2.encoder.layer_norm.bias", "g32"),
-                      part, Me, d, (*drop, mring[0]) if drop[0] > 0 else None)
+        self.head.backward(d16, hs[L], w["dA"], ring[0], w["head"], Me, part, freeze=self.freeze_base,
+                           drop=self.dropout_site("final", training=tr), xdrop=(*drop, mring[0]) if drop[0] > 0 else None)
         done("head")
+        if self.freeze_base:
+            return
         # Weight gradients on their own stream: dW = dY^T X feeds only the optimiser, so a layer's weight-gradient launch
         # (MFMA-bound, 256x256 tiles, one workgroup per CU) runs beside the NEXT layer's data-gradient chain (128x128-tile
         # GEMMs, attention backward, LayerNorm backward: VALU / HBM-bound kernels and GEMM tails that leave matrix pipes
@@ -772,9 +692,6 @@ class Wav2Vec2CTCEngine(Engine):
             matrix_range=lambda l: self.shard_ranges()[f"layer{l}"], done=done, below=branch_site, mring=mring,
             **({} if rows is None else dict(rows=rows)))
         # dh: gradient wrt h[0] = h0m + gelu(pc_pre)
-        G, K = s.num_conv_pos_embedding_groups, s.num_conv_pos_embeddings
-        Cg = d // G
-        Tpad = T + K
         # (hidden dropout on h0 + pos_conv(h0): both terms see the masked gradient)
         dg = dhm if branch_site(0)[0] > 0 else dh
         if rows is not None:
@@ -785,68 +702,17 @@ class Wav2Vec2CTCEngine(Engine):
             pc = self.dropout_site("pos_conv", training=tr)
             if pc[0] > 0:
                 ops.dropout(dg, dg, M * d, *pc)
-        ops.dgelu_mul(dg, w["pc_pre"], dpc, M * d)
-        ops.colsum(dpc, d, M, d, g32, part, out_off=o("wav2vec2.encoder.pos_conv_embed.conv.bias"))
-        # weight gradient in GEMM layout [G][Cg][K][Cg], then through the weight norm
-        ops.gemm(dpc, w["xg"], w["dwf"], M=Cg, N=K * Cg, K=M, a_layout=MNMAJOR, lda=d, b_layout=MNMAJOR,
-                 ldb=Cg, b_kseg=T, b_kseg_stride=G * Tpad * Cg, ldc=K * Cg, batch2=G, sA=(0, Cg),
-                 sB=(0, Tpad * Cg), sC=(0, Cg * K * Cg), out_f32=True)
-        pre = "wav2vec2.encoder.pos_conv_embed.conv.parametrizations.weight."
-        ops.posconv_weight_bwd(w["dwf"], st.view(pre + "original1"), st.view(pre + "original0"), self.pc_norm,
-                               st.view(pre + "original1", "g32"), st.view(pre + "original0", "g32"),
-                               self.pc_partial, d, Cg, K)
-        # data gradient: correlation of the (left 63 / right 64) padded dpc with flipped weights
-        ops.regroup_pad(dpc, w["dxg"], B, T, G, Cg, K // 2)
         dh0 = w["dA"]
-        ops.gemm(w["dxg"], self.pc_wb, dh0, M=T, N=Cg, K=K * Cg, lda=Cg, ldb=K * Cg, ldc=d, a_off=Cg,
-                 epilogue=EPI_RESIDUAL, R=dg, ldr=d, batch1=B, batch2=G, sA=(G * Tpad * Cg, Tpad * Cg),
-                 sB=(0, Cg * K * Cg), sC=(T * d, Cg), sR=(T * d, Cg))
+        self.pos_conv.backward(dg, dpc, dh0, w["pc"], B, T, part)
         # SpecAugment / padding backward: masked rows feed masked_spec_embed, then are zeroed
         if sv["tm"] is not None:
-            ops.colsum(dh0, d, M, d, g32, part, rowmask=sv["tm"], out_off=o("wav2vec2.masked_spec_embed"))
+            ops.colsum(dh0, d, M, d, st.g32, part, rowmask=sv["tm"], out_off=st.off("wav2vec2.masked_spec_embed"))
         ops.mask_frames(dh0, sv["tm"], sv["fm"], self.zero_embed, flen, B, T, d)
-        pf = self.dropout_site("feat_proj", training=tr)
-        if pf[0] > 0:  # (the projection's output was dropped before SpecAugment / padding)
-            ops.dropout(dh0, dh0, M * d, *pf)
-        # feature projection
-        fp = "wav2vec2.feature_projection."
-        C6 = s.conv_dim[6]
-        ops.colsum(dh0, d, M, d, g32, part, out_off=o(fp + "projection.bias"))
-        ops.gemm(dh0, w["xln"], g32, M=d, N=C6, K=M, a_layout=MNMAJOR, lda=d, b_layout=MNMAJOR, ldb=C6,
-                 ldc=C6, c_off=o(fp + "projection.weight"), out_f32=True, accumulate=acc)
-        dxln = w["dy"]
-        ops.gemm(dh0, p16, dxln, M=M, N=C6, K=d, lda=d, b_layout=MNMAJOR, ldb=C6, ldc=C6,
-                 b_off=o(fp + "projection.weight"))
-        ops.layernorm_bwd(dxln, w["a"][6], st.view(fp + "layer_norm.weight"), None, w["fp_stats"], None,
-                          w["dconv"][6], st.view(fp + "layer_norm.weight", "g32"),
-                          st.view(fp + "layer_norm.bias", "g32"), part, M, C6)
-        # conv stack 6..1
-        for i in range(6, 0, -1):
-            pi = f"wav2vec2.feature_extractor.conv_layers.{i}."
-            k, sd, Ci, Co = s.conv_kernel[i], s.conv_stride[i], s.conv_dim[i - 1], s.conv_dim[i]
-            Lin, Ti = Ts[i - 1], Ts[i]
-            dy = w["dy"]
-            ops.layernorm_bwd(w["dconv"][i], w["y"][i], st.view(pi + "layer_norm.weight"),
-                              st.view(pi + "layer_norm.bias"), w["cstats"][i], None, dy,
-                              st.view(pi + "layer_norm.weight", "g32"), st.view(pi + "layer_norm.bias", "g32"),
-                              part, B * Ti, Co, act=1)
-            ops.colsum(dy, Co, B * Ti, Co, g32, part, out_off=o(pi + "conv.bias"))
-            # weight gradient: one TN GEMM per utterance (batch dimension) into fp32 partials, summed
-            # afterwards -- the single long-K GEMM has only Co/128 x k*Ci/128 = 48 tiles
-            ops.gemm(dy, w["a"][i - 1], w["dwr_part"], M=Co, N=k * Ci, K=Ti, a_layout=MNMAJOR, lda=Co,
-                     b_layout=MNMAJOR, ldb=sd * Ci, ldc=k * Ci, out_f32=True, batch2=B, sA=(0, Ti * Co),
-                     sB=(0, Lin * Ci), sC=(0, Co * k * Ci))
-            ops.reduce_rows(w["dwr_part"], B, Co * k * Ci, Co * k * Ci, w["dwr"])
-            ops.conv_weight_grad_reorder(w["dwr"], g32, Co, Ci, k, dw_off=o(pi + "conv.weight"))
-            ops.gemm(dy, self.conv_wr[i], w["dcol"], M=B * Ti, N=k * Ci, K=Co, lda=Co, b_layout=MNMAJOR,
-                     ldb=k * Ci, ldc=k * Ci)
-            ops.col2im_1d(w["dcol"], w["dconv"][i - 1], B, Ti, Lin, Ci, k, sd)
-        p0 = "wav2vec2.feature_extractor.conv_layers.0."
-        ops.conv0_bwd(x, st.view(p0 + "conv.weight"), st.view(p0 + "conv.bias"),
-                      st.view(p0 + "layer_norm.weight"), st.view(p0 + "layer_norm.bias"), w["dconv"][0],
-                      st.view(p0 + "conv.weight", "g32"), st.view(p0 + "conv.bias", "g32"),
-                      st.view(p0 + "layer_norm.weight", "g32"), st.view(p0 + "layer_norm.bias", "g32"),
-                      part, B, N, s.conv_dim[0], s.conv_kernel[0], s.conv_stride[0], s.layer_norm_eps)
+        # (the projection's output was dropped before SpecAugment / padding)
+        fe = w["fe"]
+        self.feature_projection.backward(dh0, fe["a"][-1], fe["dy"], fe["dconv"][-1], w["fp"], M, part,
+                                         self.dropout_site("feat_proj", training=tr))
+        self.feature_encoder.backward(x, fe, B, N)
         done("front")
 
     def _scale_scalar(self, v: float) -> torch.Tensor:

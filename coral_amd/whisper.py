@@ -29,6 +29,7 @@ from . import ops
 from .blocks import CrossAttnBlock, FFNBlock, SelfAttnBlock, zeros_on
 from .engine import Engine
 from .ops import EPI_GELU, EPI_GELU_RESIDUAL
+from .stem_blocks import LMHead, StridedConvBlock
 from .wav2vec2 import ParamStore, _r8
 from .whisper_decode import WhisperDecoding, check_beam_arguments  # noqa: F401  (check_beam_arguments: imported from here)
 
@@ -170,8 +171,15 @@ class WhisperEngine(WhisperDecoding, Engine):
         assert shape.d_model % 8 == 0 and shape.num_mel_bins % 8 == 0
         self.store = ParamStore(whisper_param_list(shape), self.device)
         d = shape.d_model
-        self.conv1_wr = torch.zeros(d * 3 * shape.num_mel_bins, dtype=torch.bfloat16, device=self.device)
-        self.conv2_wr = torch.zeros(d * 3 * d, dtype=torch.bfloat16, device=self.device)
+        # the stem on time-padded clips of 2 T + 2 rows: conv1 (k 3, padding 1) writes rows 1 .. 2 T, conv2 (k 3, stride 2,
+        # padding 1) reads all of them
+        rows = 2 * shape.max_source_positions + 2
+        self.conv1 = StridedConvBlock(self.store, "model.encoder.conv1.weight", "model.encoder.conv1.bias", shape.num_mel_bins,
+                                      d, 3, 1, rows_in=rows, rows_out=rows, y_off=1)
+        self.conv2 = StridedConvBlock(self.store, "model.encoder.conv2.weight", "model.encoder.conv2.bias", d, d, 3, 2,
+                                      rows_in=rows)
+        self.head = LMHead(self.store, "model.decoder.layer_norm", "model.decoder.embed_tokens.weight", None, d,
+                           shape.vocab_size, shape.layer_norm_eps)
         self.mel_filters = torch.from_numpy(mel_filter_bank(shape.num_mel_bins)).to(self.device)
         self.zero_mel = torch.zeros(shape.num_mel_bins, dtype=torch.bfloat16, device=self.device)  # SpecAugment's fill
         st, eps = self.store, shape.layer_norm_eps
@@ -212,10 +220,13 @@ class WhisperEngine(WhisperDecoding, Engine):
         return {n: self.store.view(n).detach().clone() for n in self.exported_names()}
 
     def refresh_compute_weights(self):
-        s, st = self.s, self.store
-        st.refresh_bf16()
-        ops.conv_weight_reorder(st.p32, self.conv1_wr, s.d_model, s.num_mel_bins, 3, w_off=st.off("model.encoder.conv1.weight"))
-        ops.conv_weight_reorder(st.p32, self.conv2_wr, s.d_model, s.d_model, 3, w_off=st.off("model.encoder.conv2.weight"))
+        self.store.refresh_bf16()
+        self.refresh_derived()
+
+    def refresh_derived(self, part: str | None = None):
+        """The conv stem's weights are consumed in the reordered [Co][k][Ci] layout."""
+        self.conv1.refresh()
+        self.conv2.refresh()
 
     # ---- front end ---------------------------------------------------------------------------
     def log_mel(self, waves: torch.Tensor) -> torch.Tensor:
@@ -235,9 +246,7 @@ class WhisperEngine(WhisperDecoding, Engine):
         forward keeps the two pre-activations (None: not written); mask_time / mask_feature: SpecAugment masks on the
         device, u8 [B, 3000] / [B, mels]."""
         s, st = self.s, self.store
-        o = st.off
         B, mels, Tin = x.shape
-        T, d = s.max_source_positions, s.d_model
         # channels-last, time-padded input: rows 1..3000 of each clip hold the frames
         for b in range(B):
             ops.transpose_f32_bf16(x[b], w["xin"][(b * (Tin + 2) + 1) * mels:], mels, Tin)
@@ -246,34 +255,16 @@ class WhisperEngine(WhisperDecoding, Engine):
                 fm = mask_feature[b:b + 1].contiguous() if mask_feature is not None else None
                 ops.mask_frames(w["xin"][(b * (Tin + 2) + 1) * mels:], tm, fm, self.zero_mel, None, 1, Tin, mels)
         # conv1 (k=3, p=1) + GELU -> padded [B, 3002, d]
-        ops.gemm(w["xin"], self.conv1_wr, pre[0], C2=w["c1"], c_off=d, c2_off=d, M=Tin, N=d, K=3 * mels, lda=mels,
-                 ldb=3 * mels, ldc=d, bias=st.p32, bias_off=o("model.encoder.conv1.bias"), epilogue=EPI_GELU, batch2=B,
-                 sA=(0, (Tin + 2) * mels), sC=(0, (Tin + 2) * d))
+        self.conv1.forward(w["xin"], pre[0], B, C2=w["c1"], epilogue=EPI_GELU)
         # conv2 (k=3, s=2, p=1) + GELU + sinusoidal positions
-        ops.gemm(w["c1"], self.conv2_wr, pre[1], C2=h, M=T, N=d, K=3 * d, lda=2 * d, ldb=3 * d, ldc=d, bias=st.p32,
-                 bias_off=o("model.encoder.conv2.bias"), epilogue=EPI_GELU_RESIDUAL, R=st.p16,
-                 r_off=o("model.encoder.embed_positions.weight"), ldr=d, batch2=B, sA=(0, (Tin + 2) * d), sC=(0, T * d),
-                 sR=(0, 0))
+        self.conv2.forward(w["c1"], pre[1], B, C2=h, epilogue=EPI_GELU_RESIDUAL, R=st.p16,
+                           r_off=st.off("model.encoder.embed_positions.weight"), ldr=s.d_model, sR=(0, 0))
 
     def _embed(self, ids, pos, h, M):
         """The decoder's input rows: token + position embeddings of int32 ids / positions on the device."""
         p16, o = self.store.p16, self.store.off
         ops.embed_tokens(p16[o("model.decoder.embed_tokens.weight"):], p16[o("model.decoder.embed_positions.weight"):],
                          ids, pos, h, M, self.s.d_model)
-
-    def _head(self, h, hf, M, logits=None, stats=None, last_of=None):
-        """The decoder's final LayerNorm (h -> hf, M rows) and the tied output projection: fp32 logits [rows, Vp] of every
-        row, or with last_of=B of the last row of each of B sequences, into `logits` (default: a fresh buffer)."""
-        s, st = self.s, self.store
-        d, V, Vp = s.d_model, s.vocab_size, _r8(s.vocab_size)
-        ops.layernorm_fwd(h, st.view("model.decoder.layer_norm.weight"), st.view("model.decoder.layer_norm.bias"), hf, stats,
-                          M, d, s.layer_norm_eps)
-        rows, n = (hf, M) if last_of is None else (hf.view(last_of, M // last_of, d)[:, -1, :].contiguous(), last_of)
-        if logits is None:
-            # (torch.empty: the GEMM writes all V columns, the Vp - V pad columns are never read - no fill kernel per call)
-            logits = torch.empty(n, Vp, dtype=torch.float32, device=self.device)
-        ops.gemm(rows, st.p16, logits, M=n, N=V, K=d, lda=d, ldb=d, ldc=Vp, b_off=st.off("model.decoder.embed_tokens.weight"))
-        return logits
 
     # ---- encoder -----------------------------------------------------------------------------
     def _encoder_ws(self, B):
@@ -360,7 +351,7 @@ class WhisperEngine(WhisperDecoding, Engine):
         s = self.s
         d, H, Te = s.d_model, s.decoder_attention_heads, s.max_source_positions
         z = zeros_on(self.device)
-        w = dict(h=[z(B * L * d), z(B * L * d)], hf=z(B * L * d))
+        w = dict(h=[z(B * L * d), z(B * L * d)], **self.head.alloc(B * L, z, train=False))  # (the head's: "hf")
         for sa, ca, ff in self.dec_blocks[:1]:  # (every layer's blocks have the same shapes)
             w.update(sa=sa.alloc(B, L, z, train=False), ca=ca.alloc(B, L, Te, z, train=False), ff=ff.alloc(B * L, z, train=False))
         # one decoded token per clip: the cross-attention may deal a (clip, head)'s 1500 keys to several workgroups
@@ -391,8 +382,8 @@ class WhisperEngine(WhisperDecoding, Engine):
             h0, h1 = h1, h0
         V, Vp = s.vocab_size, _r8(s.vocab_size)
         if last_only:
-            return self._head(h0, w["hf"], M, last_of=B).view(B, 1, Vp)[:, :, :V]
-        logits = self._last_logits = self._head(h0, w["hf"], M)
+            return self.head.forward(h0, w, M, last_of=B).view(B, 1, Vp)[:, :, :V]
+        logits = self._last_logits = self.head.forward(h0, w, M)
         return logits.view(B, L, Vp)[:, :, :V]
 
     # ---- model-level API -------------------------------------------------------------------------

@@ -209,7 +209,7 @@ class WhisperDecoding:
             ca.forward(h1, h0, w["ca"], B, n, Te, kv=cross_kv[l])
             ff.forward(h0, h1, w["ff"], M)
             h0, h1 = h1, h0
-        logits = self._head(h0, w["hf"], M, last_of=B)
+        logits = self.head.forward(h0, w, M, last_of=B)
         cache["pos"] = pos0 + n
         return logits[:, :s.vocab_size]
 
@@ -351,7 +351,7 @@ class WhisperDecoding:
                      epilogue=EPI_RESIDUAL, R=h1, ldr=d)
             ff.forward(h0, h1, w["ff"], R)
             h0, h1 = h1, h0
-        self._head(h0, w["hf"], R, logits=g["logits"])
+        self.head.forward(h0, w, R, logits=g["logits"])
 
     def _pick_advance(self, g: dict, logits: torch.Tensor, ldv: int, suppress: torch.Tensor):
         """The pick of a greedy step and the step's bookkeeping in one launch: out[b, pos + 1] = the token (pad for
@@ -609,9 +609,7 @@ class WhisperDecoding:
                 # WhisperNoSpeechDetection: the softmax of the raw logits at the start-of-transcript position, i.e. the
                 # head on prefix position 0 (decode_step left the final LayerNorm of every prefix row in the workspace)
                 hf0 = self._decoder_ws(B, P)["hf"][:B * P * s.d_model].view(B, P, s.d_model)[:, 0, :].contiguous()
-                lg0 = torch.empty(B, _r8(V), dtype=torch.float32, device=dev)
-                ops.gemm(hf0, self.store.p16, lg0, M=B, N=V, K=s.d_model, lda=s.d_model, ldb=s.d_model, ldc=_r8(V),
-                         b_off=self.store.off("model.decoder.embed_tokens.weight"))
+                lg0 = self.head.project(hf0, B)
                 sc["no_speech_prob"] = torch.empty(B, dtype=torch.float32, device=dev)
                 ops.row_token_prob(lg0, sc["no_speech_prob"], B, V, _r8(V), scoring.no_speech_token)
         # the first free token through the step's own pick (a scored one counts its log-probability): the books stand at

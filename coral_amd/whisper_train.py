@@ -19,8 +19,7 @@ import torch
 from . import ops
 from .staging import PinnedStager
 from .blocks import Scratch, _z, encoder_backward, wgrad_stream, zeros_on
-from .ops import MNMAJOR
-from .wav2vec2 import _r8
+from .stem_blocks import ConvScratch
 from .whisper import WhisperEngine, WhisperShape, shift_tokens_right
 
 
@@ -222,12 +221,6 @@ class WhisperTrainEngine(WhisperEngine):
         """The encoder layers' weight matrices: the gradient norm needs no pass over them."""
         return [(l, *m) for l in range(self.s.encoder_layers) for m in self._enc_matrices(l)]
 
-    def refresh_derived(self, part: str | None = None):
-        """conv stem weights are consumed in the reordered [Co][k][Ci] layout."""
-        s, st = self.s, self.store
-        ops.conv_weight_reorder(st.p32, self.conv1_wr, s.d_model, s.num_mel_bins, 3, w_off=st.off("model.encoder.conv1.weight"))
-        ops.conv_weight_reorder(st.p32, self.conv2_wr, s.d_model, s.d_model, 3, w_off=st.off("model.encoder.conv2.weight"))
-
     def __call__(self, input_features, labels, mask_time=None, mask_feature=None, enc_keep=None, dec_keep=None):
         """Trainer-facing call: returns an object with `.loss` (device scalar) and `.logits`."""
         from .wav2vec2 import CTCOutput
@@ -259,11 +252,10 @@ class WhisperTrainEngine(WhisperEngine):
             eh=[_z(Me * d, dev) for _ in range(2 * s.encoder_layers + 1)], enc_out=_z(Me * d, dev),
             enc_st=_z(Me * 2, dev, f32),
             enc_sv=[(sa.alloc(B, T, z), ff.alloc(Me, z)) for sa, ff in self.enc_blocks],
-            dh=[_z(Md * d, dev) for _ in range(3 * s.decoder_layers + 1)], dec_out=_z(Md * d, dev),
-            dec_st=_z(Md * 2, dev, f32),
+            dh=[_z(Md * d, dev) for _ in range(3 * s.decoder_layers + 1)], head=self.head.alloc(Md, z),
             dec_sv=[(sa.alloc(B, L, z), ca.alloc(B, L, T, z), ff.alloc(Md, z)) for sa, ca, ff in self.dec_blocks],
-            logits=_z(Md * _r8(s.vocab_size), dev, f32), dlogits=_z(Md * _r8(s.vocab_size), dev, f32),
-            dlogits16=_z(Md * _r8(s.vocab_size), dev),
+            logits=_z(Md * self.head.Vp, dev, f32), dlogits=_z(Md * self.head.Vp, dev, f32),
+            dlogits16=_z(Md * self.head.Vp, dev),
             loss_cnt=_z(2, dev, f32),  # loss_sum (fp32) | count (int32) in adjacent words: cleared by one launch
             sc_e=Scratch(Me, d, s.encoder_ffn_dim, z), sc_d=Scratch(Md, d, s.decoder_ffn_dim, z, Mkv=Me),
             # (second scratch / bias workspace and three more gradient buffers: the encoder layers' weight gradients run
@@ -275,9 +267,9 @@ class WhisperTrainEngine(WhisperEngine):
             ln_part_e=[[_z(ops.layernorm_bwd_partial_floats(Me, d), dev, f32) for _ in range(2)] for _ in range(2)],
             ln_part_d=[_z(ops.layernorm_bwd_partial_floats(Md, d), dev, f32) for _ in range(3)],
             bias_ws=_z(ops.COLSUM_PARTS * (5 * d + s.encoder_ffn_dim), dev, f32),
-            bias_ws2=_z(ops.COLSUM_PARTS * (5 * d + s.encoder_ffn_dim), dev, f32), denc32=_z(Me * d, dev, f32), dpre=_z(B * (Tin + 2) * d + 64, dev),
-            dcol=_z(Me * 3 * d, dev), dwr_part=_z(B * d * 3 * max(d, s.num_mel_bins), dev, f32),
-            dwr=_z(d * 3 * max(d, s.num_mel_bins), dev, f32))
+            bias_ws2=_z(ops.COLSUM_PARTS * (5 * d + s.encoder_ffn_dim), dev, f32), denc32=_z(Me * d, dev, f32), dpre=_z(B * (Tin + 2) * d + 64, dev))
+        # the stem's backward scratch: both weight gradients, conv2's data gradient (conv1's input has none)
+        w["conv_sc"] = ConvScratch(z, B, (self.conv1, self.conv2), (self.conv2,), w["sc_e"].part)
         f8 = self._fp8_train
         if f8 is not None:
             Me = B * s.max_source_positions
@@ -384,8 +376,8 @@ class WhisperTrainEngine(WhisperEngine):
             ff.forward(w["dh"][3 * l + 2], w["dh"][3 * l + 3], sv_f, Md, drop, self.step_seed * 4096 + 2048 + l,
                        hdrop=hd(2816 + l))
         self._await_all()  # decf and anything not waited for above
-        self._head(w["dh"][-1], w["dec_out"], Md, logits=w["logits"], stats=w["dec_st"])
-        V, Vp = s.vocab_size, _r8(s.vocab_size)
+        self.head.forward(w["dh"][-1], w["head"], Md, logits=w["logits"])
+        V, Vp = s.vocab_size, self.head.Vp
         ops.clear_ranges(w["loss_cnt"], ((0, 2),))  # loss_sum | count (adjacent 4-byte words): one launch
         w["loss_sum"], w["count"] = w["loss_cnt"][0:1], w["loss_cnt"][1:2].view(torch.int32)
         lab32 = self._stager.to_device(lab, torch.int32, "lab").view(-1)
@@ -404,27 +396,21 @@ class WhisperTrainEngine(WhisperEngine):
         sv = self._saved
         s, st = self.s, self.store
         w, B, L = sv["w"], sv["B"], sv["L"]
-        p16, g32, o = st.p16, st.g32, st.off
+        g32, o = st.g32, st.off
         if self._fp8_train is not None:
             self._fp8_train["bwd_seen"] = True  # (this backward measures the amax of the gradients entering fc1)
         T, d = s.max_source_positions, s.d_model
         Tin = 2 * T
         Me, Md = B * T, B * L
-        V, Vp = s.vocab_size, _r8(s.vocab_size)
-        mels = s.num_mel_bins
+        Vp = self.head.Vp
         sc_e, sc_d = w["sc_e"], w["sc_d"]
         # mean over the non-ignored tokens, then bf16 for the MFMA path
         w["dlogits"].mul_(sv["inv_count"] * loss_scale)
         ops.cast_f32_bf16(w["dlogits"], w["dlogits16"], Md * Vp)
         dl = w["dlogits16"]
         # tied LM head: dE += dlogits^T hf ; dhf = dlogits E
-        ops.gemm(dl, w["dec_out"], g32, M=V, N=d, K=Md, a_layout=MNMAJOR, lda=Vp, b_layout=MNMAJOR, ldb=d, ldc=d,
-                 c_off=o("model.decoder.embed_tokens.weight"), out_f32=True, accumulate=True)
         ga, gb = w["g_d"][:2]
-        ops.gemm(dl, p16, ga, M=Md, N=d, K=V, lda=Vp, b_layout=MNMAJOR, ldb=d, ldc=d, b_off=o("model.decoder.embed_tokens.weight"))
-        ops.layernorm_bwd(ga, w["dh"][-1], st.view("model.decoder.layer_norm.weight"), None, w["dec_st"], None, gb,
-                          st.view("model.decoder.layer_norm.weight", "g32"), st.view("model.decoder.layer_norm.bias", "g32"),
-                          sc_d.part, Md, d)
+        self.head.backward(dl, w["dh"][-1], ga, gb, w["head"], Md, sc_d.part)
         ops.clear_f32(w["denc32"], w["denc32"].numel())
         # Decoder layers.  The six token-side weight gradients of a layer (K = B*L rows: 16 ... 64 tiles of the 256x256
         # kernel each, 224 together at whisper-medium) go out as ONE grouped launch at the end of the layer, with their
@@ -497,24 +483,10 @@ class WhisperTrainEngine(WhisperEngine):
             ops.dropout(cur, cur, Me * d, ep, eseed)
         dpre2 = other
         ops.dgelu_mul(cur, w["pre2"], dpre2, Me * d)
-        ops.colsum(dpre2, d, Me, d, g32, sc_e.part, out_off=o("model.encoder.conv2.bias"))
-        ops.gemm(dpre2, w["c1"], w["dwr_part"], M=d, N=3 * d, K=T, a_layout=MNMAJOR, lda=d, b_layout=MNMAJOR, ldb=2 * d,
-                 ldc=3 * d, out_f32=True, batch2=B, sA=(0, T * d), sB=(0, (Tin + 2) * d), sC=(0, d * 3 * d))
-        ops.reduce_rows(w["dwr_part"], B, d * 3 * d, d * 3 * d, w["dwr"])
-        ops.conv_weight_grad_reorder(w["dwr"], g32, d, d, 3, dw_off=o("model.encoder.conv2.weight"))
-        ops.gemm(dpre2, self.conv2_wr, w["dcol"], M=Me, N=3 * d, K=d, lda=d, b_layout=MNMAJOR, ldb=3 * d, ldc=3 * d)
-        ops.col2im_1d(w["dcol"], w["dpre"], B, T, Tin + 2, d, 3, 2)  # gradient wrt the padded gelu(pre1)
+        self.conv2.backward(dpre2, w["c1"], B, w["conv_sc"], dx=w["dpre"])  # dpre: gradient wrt the padded gelu(pre1)
         # conv1: rows 1..3000 of every clip (the padding rows carry no parameter gradient)
         ops.dgelu_mul(w["dpre"], w["pre1"], w["dpre"], B * (Tin + 2) * d)
-        part_n = ops.colsum_partial_floats(Tin, d)
-        for b in range(B):
-            ops.colsum(w["dpre"], d, Tin, d, g32, sc_e.part[:part_n], x_off=(b * (Tin + 2) + 1) * d,
-                       out_off=o("model.encoder.conv1.bias"))
-        ops.gemm(w["dpre"], w["xin"], w["dwr_part"], M=d, N=3 * mels, K=Tin, a_layout=MNMAJOR, lda=d, a_off=d,
-                 b_layout=MNMAJOR, ldb=mels, ldc=3 * mels, out_f32=True, batch2=B, sA=(0, (Tin + 2) * d),
-                 sB=(0, (Tin + 2) * mels), sC=(0, d * 3 * mels))
-        ops.reduce_rows(w["dwr_part"], B, d * 3 * mels, d * 3 * mels, w["dwr"])
-        ops.conv_weight_grad_reorder(w["dwr"], g32, d, mels, 3, dw_off=o("model.encoder.conv1.weight"))
+        self.conv1.backward(w["dpre"], w["xin"], B, w["conv_sc"])
         done("front")
 
     def clear_internal_grads_of(self, prefix: str):

@@ -119,7 +119,7 @@ def decode_ws_bytes(B, d, f, H, n_layers):
 class CaAttnDesc(C.Structure):
     """Mirror of `CaAttnDesc` in include/coral_amd.h."""
 
-    _fields_ = ([(n, C.c_void_p) for n in ("Q", "K", "V", "O", "dO", "dQ", "dK", "dV", "lse", "Dq", "klen", "key_slot")]
+    _fields_ = ([(n, C.c_void_p) for n in ("Q", "K", "V", "O", "dO", "dQ", "dK", "dV", "lse", "Dq", "klen", "key_slot", "kstart")]
                 + [(n, C.c_int64) for n in ("ldq", "ldk", "ldv", "ldo", "lddo", "lddq", "lddk", "lddv",
                                              "sqb", "skb", "svb", "sob", "sdob", "sdqb", "sdkb", "sdvb")]
                 + [(n, C.c_int32) for n in ("B", "H", "Tq", "Tk", "hd", "Tqp", "causal")]

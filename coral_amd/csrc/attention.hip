@@ -23,6 +23,9 @@ static int attn_plan_error(int error, const char* who) {
                "%s: O8 needs a scale, >= 100 queries per head (the wide kernels) and 8-byte aligned rows", who);
   CA_CHECK_ARG(error != ATTN_PLAN_SPLIT_WS, "attention: split_ws needs CA_ATTN_SPLIT_WS_BYTES(B, H) bytes, 16-byte aligned");
   CA_CHECK_ARG(error != ATTN_PLAN_KEY_SLOT_BWD, "%s: key_slot is a forward (decode) option", who);
+  CA_CHECK_ARG(error != ATTN_PLAN_KSTART,
+               "%s: kstart needs ca_attn_fwd with a causal mask, or with Tq == 1 and klen; head_dim <= 64 and no dropout, "
+               "O8, row_off, split_ws or key_slot", who);
   return CA_OK;
 }
 static AttnArgs to_args(const CaAttnDesc& d) {
@@ -41,6 +44,7 @@ static AttnArgs to_args(const CaAttnDesc& d) {
   a.qp_x = nullptr; a.qp_ldx = 0; a.qp_gamma = a.qp_beta = a.qp_bias = nullptr; a.qp_W = nullptr; a.qp_ldw = 0; a.qp_d = 0;
   a.qp_eps = 0.f;
   a.nsplit = 1; a.split_slab = nullptr; a.split_cnt = nullptr;
+  a.kstart = d.kstart;
   return a;
 }
 // the single-query kernel's key split: arrival counters at the front of the caller's workspace, partial slabs behind

@@ -334,7 +334,22 @@ struct AttnArgs {
   int64_t qp_ldw;
   int qp_d;
   float qp_eps;
+  const int32_t* kstart;        // [B] or null: the KM forward instantiations, first key of each row (CaAttnDesc.kstart)
 };
+// A per-row first key (CaAttnDesc.kstart) is a shift of the row's keys: the K / V base moves kstart[b] rows on and the key
+// counts shrink by as much, so the loops, masks and tile loaders of a kernel stay what they are and run in shifted key
+// indices (a causal compare then takes the query index shifted too: attn_kstart_shift's return value).  Keys in front of
+// kstart[b] are never loaded; a row left without keys runs no tile and stores zeros.  Workgroup-uniform.
+__device__ __forceinline__ int attn_kstart_shift(const AttnArgs& a, int b, const unsigned short*& K, const unsigned short*& V,
+                                                 int& Tk, int& kl) {
+  int ks = a.kstart[b];
+  ks = ks < 0 ? 0 : (ks > kl ? kl : ks);
+  K += (int64_t)ks * a.ldk;
+  V += (int64_t)ks * a.ldv;
+  Tk -= ks;
+  kl -= ks;
+  return ks;
+}
 // Flat index of probability (b, h, q, key): rows are padded to a multiple of 4 keys so that 4 consecutive keys from a
 // multiple of 4 share one hash (ca_dropout_keep4); the backward kernels regenerate the forward's decisions from it.
 __device__ __forceinline__ uint64_t attn_drop_index(const AttnArgs& a, int b, int h, int q, int key) {

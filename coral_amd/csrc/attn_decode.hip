@@ -34,7 +34,8 @@ __device__ __forceinline__ void glds16_async(const void* g, char* lds_wave_base)
 // KS (CaAttnDesc.key_slot, beam search): key / value t of query row b comes from cache row key_slot[b, t] instead of row b.
 // The row's table is copied into LDS behind the V rings before the first tile is asked for, so the loop's address
 // arithmetic gains one LDS read per row and its vector-memory sequence - and the counted waits - stay what they are.
-template <int HDPV, bool QP = false, int DT = 3, bool KS = false>
+// KM (CaAttnDesc.kstart): the row's keys start at kstart[b] - attn_kstart_shift in the prologue, nothing else changes.
+template <int HDPV, bool QP = false, int DT = 3, bool KS = false, bool KM = false>
 __global__ __launch_bounds__(256) void attn_fwd_smallq_kernel(const AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NKS = HDPV / 32, NNB = HDPV / 16;
@@ -59,8 +60,9 @@ __global__ __launch_bounds__(256) void attn_fwd_smallq_kernel(const AttnArgs a) 
   const unsigned short* V = a.V + (KS ? 0 : b * a.svb) + h * hd;
   char* Vring = smem + wave * D * IMG;
   const int qrow = r < a.Tq ? r : a.Tq - 1;
-  int kl = a.Tk;
+  int Tk = a.Tk, kl = a.Tk;
   if (a.klen) kl = a.klen[b] < kl ? a.klen[b] : kl;
+  if constexpr (KM) attn_kstart_shift(a, b, K, V, Tk, kl);
   const int* slot = (const int*)(smem + 4 * D * IMG);  // KS: [Tk] cache rows of this query row's keys
   if constexpr (KS) {
     int* sw = (int*)(smem + 4 * D * IMG);
@@ -194,7 +196,7 @@ __global__ __launch_bounds__(256) void attn_fwd_smallq_kernel(const AttnArgs a) 
 #pragma unroll
     for (int blk = 0; blk < 4; ++blk) {
       int key = kt * 64 + 32 * (blk >> 1) + rowperm(blk & 1, r);
-      key = key < a.Tk ? key : a.Tk - 1;  // clamped rows are masked below (key >= kl)
+      key = key < Tk ? key : Tk - 1;  // clamped rows are masked below (key >= kl)
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks) {
         const int dim = 32 * ks + 8 * g;
@@ -210,7 +212,7 @@ __global__ __launch_bounds__(256) void attn_fwd_smallq_kernel(const AttnArgs a) 
       const int c = (lane % PC) ^ mnswz<PC>(kr);
       const int dim = c * 8;
       const int row = kt * 64 + kr;
-      const void* src = (row < a.Tk && dim < hd)
+      const void* src = (row < Tk && dim < hd)
                             ? (const void*)(V + (KS ? (int64_t)slot[row] * a.svb : (int64_t)0) + (int64_t)row * a.ldv + dim)
                             : (const void*)g_attn_zero_page;
       glds16_async(src, img + i * 1024);
@@ -430,9 +432,9 @@ __global__ __launch_bounds__(256) void attn_fwd_smallq_kernel(const AttnArgs a) 
         for (int w = 0; w < 4; ++w) v = fmaf(co[(w * 16 + q) * HDPV + n], wgt[w], v);
         if (n < hd) O[(int64_t)q * a.ldo + n] = f2bf(v * inv);
       }
-      if (r == 0 && a.lse)
+      if (r == 0 && a.lse)  // (KM: a row whose first key lies behind its last writes nothing that is not finite)
         a.lse[((int64_t)b * a.H + h) * a.Tqp + q] = L > 0.f ? (M + __builtin_amdgcn_logf(L)) * 0.69314718055994530942f
-                                                            : __builtin_inff();
+                                                            : (KM ? 0.f : __builtin_inff());
     }
   }
 }
@@ -440,14 +442,14 @@ __global__ __launch_bounds__(256) void attn_fwd_smallq_kernel(const AttnArgs a) 
 // ---- launcher ---------------------------------------------------------------------------------------------------------
 // The rings need more dynamic LDS than a kernel may ask for by default: the limit is raised to the instantiation's
 // largest launch (the longest key_slot table) once per device.
-template <bool QP, int DT, bool KS>
+template <bool QP, int DT, bool KS, bool KM = false>
 static int smallq_launch(const AttnPlan& p, const AttnArgs& a, hipStream_t s, const char* who) {
   static std::atomic<uint64_t> raised{0};  // one bit per device
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) dev = 0;
   const uint64_t bit = dev < 64 ? uint64_t(1) << dev : 0;  // (devices beyond the mask: every launch)
   if (!(raised.load(std::memory_order_relaxed) & bit)) {
-    const hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_smallq_kernel<64, QP, DT, KS>,
+    const hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_smallq_kernel<64, QP, DT, KS, KM>,
                                              hipFuncAttributeMaxDynamicSharedMemorySize,
                                              (int)attn_smallq_lds(DT, QP, KS ? ATTN_KEY_SLOT_MAX_KEYS * 4 : 0));
     if (e != hipSuccess) {
@@ -456,7 +458,7 @@ static int smallq_launch(const AttnPlan& p, const AttnArgs& a, hipStream_t s, co
     }
     raised.fetch_or(bit, std::memory_order_relaxed);
   }
-  return attn_launch(attn_fwd_smallq_kernel<64, QP, DT, KS>, p, s, who, a);
+  return attn_launch(attn_fwd_smallq_kernel<64, QP, DT, KS, KM>, p, s, who, a);
 }
 int attn_launch_decode(const AttnPlan& p, const AttnArgs& a, hipStream_t s, const char* who) {
   switch (attn_inst(p)) {
@@ -467,6 +469,9 @@ int attn_launch_decode(const AttnPlan& p, const AttnArgs& a, hipStream_t s, cons
     // (non-temporal loads of the K|V stream measured slower here: 8 491 -> 8 307 audio-s/s at 128 clips, round 5)
     case attn_inst(ATTN_FWD_SMALLQ, 64, 0, 0, 3, 1, 0): return smallq_launch<true, 3, false>(p, a, s, who);
     case attn_inst(ATTN_FWD_SMALLQ, 64, 0, 0, 2, 1, 0): return smallq_launch<true, 2, false>(p, a, s, who);
+    // a per-row first key (CaAttnDesc.kstart): the decoder self-attention of a left-padded batch of prompts
+    case attn_inst(ATTN_FWD_SMALLQ, 64, 0, 0, 3, 0, 0, 1): return smallq_launch<false, 3, false, true>(p, a, s, who);
+    case attn_inst(ATTN_FWD_SMALLQ, 64, 0, 0, 2, 0, 0, 1): return smallq_launch<false, 2, false, true>(p, a, s, who);
   }
   return attn_no_kernel(p, who);
 }

@@ -10,7 +10,8 @@
 // fully inside the valid key range take a path without any per-element masking.
 // 1024 workgroups at the path's shape (8 query tiles x 128 heads): at 4 waves per SIMD they are all resident at
 // once; at 3 (148 VGPRs) a second round runs one third full.
-template <int HDPV, bool DROP = false>
+// KM (CaAttnDesc.kstart, causal): the row's keys start at kstart[b] - attn_kstart_shift; qc is the query in shifted indices.
+template <int HDPV, bool DROP = false, bool KM = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void attn_fwd_kernel(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NKS = HDPV / 32, NNB = HDPV / 16;
@@ -30,14 +31,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   const int q0 = tile * 64 + wave * 16;
   const int qi = q0 + r;  // this lane's query (column of the transposed score tile)
   const int qrow = qi < a.Tq ? qi : a.Tq - 1;
-  int kl = a.Tk;
+  int Tk = a.Tk, kl = a.Tk;
   if (a.klen) kl = a.klen[b] < kl ? a.klen[b] : kl;
+  int kshift = 0;
+  if constexpr (KM) kshift = attn_kstart_shift(a, b, K, V, Tk, kl);
+  const int qc = qi - kshift;
   // all HDPV/32 k-steps and HDPV/16 column blocks are computed: dims >= hd are zero in every LDS image
   bf16x8_t qf[NKS];
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) qf[ks] = load_rowfrag(Q, a.ldq, qrow, ks, lane, hd);
   int ntile = (kl + 63) / 64;
-  if (a.causal && ntile > tile + 1) ntile = tile + 1;  // keys beyond the tile's last query are masked
+  if constexpr (KM) {
+    const int last = tile * 64 + 63 - kshift;  // the tile's last query, shifted: below 0 = no key is allowed
+    const int nc = last >= 0 ? last / 64 + 1 : 0;
+    ntile = ntile < nc ? ntile : nc;
+  } else {
+    if (a.causal && ntile > tile + 1) ntile = tile + 1;  // keys beyond the tile's last query are masked
+  }
   const float c2 = a.scale * LOG2E;
 
   float m = NEG_BIG, l = 0.f;  // running max (log2 units, same in the 4 lanes of a query) / this lane's partial sum
@@ -49,14 +59,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   MnImgFast<64, HDPV> vfast;
   kfast.init(a.ldk, wave, lane);
   vfast.init(a.ldv, wave, lane);
-  const int nfast = fast_tiles(a.Tk, 64);
+  const int nfast = fast_tiles(Tk, 64);
   for (int kt = 0; kt < ntile; ++kt) {
     if (kt < nfast) {
       kfast.issue(Kimg, K + (int64_t)kt * 64 * a.ldk, wave);
       vfast.issue(Vimg, V + (int64_t)kt * 64 * a.ldv, wave);
     } else {
-      load_kmajor_image<64, HDPV>(Kimg, K, a.ldk, kt * 64, a.Tk, hd, wave, lane);
-      load_mnmajor_image<64, HDPV>(Vimg, V, a.ldv, kt * 64, a.Tk, hd, wave, lane);
+      load_kmajor_image<64, HDPV>(Kimg, K, a.ldk, kt * 64, Tk, hd, wave, lane);
+      load_mnmajor_image<64, HDPV>(Vimg, V, a.ldv, kt * 64, Tk, hd, wave, lane);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -78,7 +88,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int key = kt * 64 + 32 * (blk >> 1) + 8 * g + 4 * (blk & 1) + e;
-          const bool ok = key < kl && (!a.causal || key <= qi);
+          const bool ok = key < kl && (!a.causal || key <= qc);
           sc[blk][e] = ok ? sc[blk][e] : NEG_BIG;
         }
     }
@@ -137,7 +147,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   // total of the four lane groups that share a query; lse in natural-log units for the backward
   l += __shfl_xor(l, 16, 64);
   l += __shfl_xor(l, 32, 64);
-  const float lse = l > 0.f ? (m + __builtin_amdgcn_logf(l)) * 0.69314718055994530942f : __builtin_inff();
+  // (KM: a row in front of its first key has attended to nothing by design, and writes nothing that is not finite)
+  const float lse = l > 0.f ? (m + __builtin_amdgcn_logf(l)) * 0.69314718055994530942f : (KM ? 0.f : __builtin_inff());
   if (g == 0 && qi < a.Tq && a.lse) a.lse[((int64_t)b * a.H + h) * a.Tqp + qi] = lse;
   const float inv = l > 0.f ? 1.0f / l : 0.f;  // nothing attended -> zero output
   float ir[4];
@@ -172,7 +183,8 @@ using IC = std::integral_constant<int, N>;
 // softmax of tile kt inside one wave (a third image pair and a second score set, 230 registers: 5 % SLOWER - the
 // co-resident waves already overlap the two pipes, what is short is issue slots), and four waves per SIMD at 128
 // registers (27 spilled dwords: 183 us).
-template <int HDPV, bool DROP, int NW, int NST, int WPE = 2>
+// KM (CaAttnDesc.kstart, causal): as in attn_fwd_kernel; qc[] are the queries in shifted indices.
+template <int HDPV, bool DROP, int NW, int NST, int WPE = 2, bool KM = false>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void attn_fwd_wide_kernel(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NQ = 2, NKS = HDPV / 32, NNB = HDPV / 16;
@@ -197,10 +209,19 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     qi[j] = q0 + 16 * j + r;
     qrow[j] = qi[j] < a.Tq ? qi[j] : a.Tq - 1;
   }
-  int kl = a.Tk;
+  int Tk = a.Tk, kl = a.Tk;
   if (a.klen) kl = a.klen[b] < kl ? a.klen[b] : kl;
+  int kshift = 0;
+  if constexpr (KM) kshift = attn_kstart_shift(a, b, K, V, Tk, kl);
+  int qc[NQ];
+#pragma unroll
+  for (int j = 0; j < NQ; ++j) qc[j] = qi[j] - kshift;
   int ntile = (kl + 63) / 64;
-  if (a.causal) {  // keys beyond the workgroup's last query are masked
+  if constexpr (KM) {
+    const int lastq = tile * QPB + QPB - 1 - kshift;  // the workgroup's last query, shifted: below 0 = no key is allowed
+    const int last = lastq >= 0 ? lastq / 64 + 1 : 0;
+    ntile = ntile < last ? ntile : last;
+  } else if (a.causal) {  // keys beyond the workgroup's last query are masked
     const int last = (tile * QPB + QPB - 1) / 64 + 1;
     ntile = ntile < last ? ntile : last;
   }
@@ -208,15 +229,15 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
   MnImgFast<64, HDPV, NW> vfast;
   kfast.init(a.ldk, wave, lane);
   vfast.init(a.ldv, wave, lane);
-  const int nfast = fast_tiles(a.Tk, 64);
+  const int nfast = fast_tiles(Tk, 64);
   auto issue = [&](int kt, int stage) __attribute__((always_inline)) {
     char* img = smem + stage * PAIR;
     if (kt < nfast) {
       kfast.issue(img, K + (int64_t)kt * 64 * a.ldk, wave);
       vfast.issue(img + IMG, V + (int64_t)kt * 64 * a.ldv, wave);
     } else {
-      load_kmajor_image<64, HDPV, NW>(img, K, a.ldk, kt * 64, a.Tk, hd, wave, lane);
-      load_mnmajor_image<64, HDPV, NW>(img + IMG, V, a.ldv, kt * 64, a.Tk, hd, wave, lane);
+      load_kmajor_image<64, HDPV, NW>(img, K, a.ldk, kt * 64, Tk, hd, wave, lane);
+      load_mnmajor_image<64, HDPV, NW>(img + IMG, V, a.ldv, kt * 64, Tk, hd, wave, lane);
     }
   };
 #pragma unroll
@@ -281,7 +302,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const int key = kt * 64 + 32 * (blk >> 1) + 8 * g + 4 * (blk & 1) + e;
-            const bool ok = key < kl && (!a.causal || key <= qi[j]);
+            const bool ok = key < kl && (!a.causal || key <= qc[j]);
             sc[j][blk][e] = ok ? sc[j][blk][e] : NEG_BIG;
           }
       }
@@ -457,7 +478,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(WPE, WP
     float lt = l[j];
     lt += __shfl_xor(lt, 16, 64);
     lt += __shfl_xor(lt, 32, 64);
-    const float lse = lt > 0.f ? (m[j] + __builtin_amdgcn_logf(lt)) * 0.69314718055994530942f : __builtin_inff();
+    const float lse = lt > 0.f ? (m[j] + __builtin_amdgcn_logf(lt)) * 0.69314718055994530942f : (KM ? 0.f : __builtin_inff());
     if (g == 0 && qi[j] < a.Tq && a.lse) a.lse[((int64_t)b * a.H + h) * a.Tqp + qi[j]] = lse;
     const float inv = lt > 0.f ? 1.0f / lt : 0.f;  // nothing attended -> zero output
     float ir[4];
@@ -484,6 +505,10 @@ int attn_launch_fwd(const AttnPlan& p, const AttnArgs& a, hipStream_t s, const c
     case attn_inst(ATTN_FWD_WIDE, 64, 1, 2): return attn_launch(attn_fwd_wide_kernel<64, true, 4, 2, 2>, p, s, who, a);
     case attn_inst(ATTN_FWD_WIDE, 128, 0, 2): return attn_launch(attn_fwd_wide_kernel<128, false, 4, 2, 2>, p, s, who, a);
     case attn_inst(ATTN_FWD_WIDE, 128, 1, 2): return attn_launch(attn_fwd_wide_kernel<128, true, 4, 2, 2>, p, s, who, a);
+    // a per-row first key (CaAttnDesc.kstart): the causal decoder prefill, head_dim <= 64
+    case attn_inst(ATTN_FWD, 64, 0, 0, 0, 0, 0, 1): return attn_launch(attn_fwd_kernel<64, false, true>, p, s, who, a);
+    case attn_inst(ATTN_FWD_WIDE, 64, 0, 3, 0, 0, 0, 1): return attn_launch(attn_fwd_wide_kernel<64, false, 4, 2, 3, true>, p, s, who, a);
+    case attn_inst(ATTN_FWD_WIDE, 64, 0, 2, 0, 0, 0, 1): return attn_launch(attn_fwd_wide_kernel<64, false, 4, 2, 2, true>, p, s, who, a);
   }
   return attn_no_kernel(p, who);
 }

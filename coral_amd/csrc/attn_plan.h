@@ -114,7 +114,10 @@ enum AttnKernel {
   ATTN_FWD = 1, ATTN_FWD_WIDE = 2, ATTN_FWD_SMALLQ = 3, ATTN_BWD_PREP = 4, ATTN_BWD_DKV = 5, ATTN_BWD_DKV_WIDE = 6,
   ATTN_BWD_DQ = 7, ATTN_BWD_DQ_WIDE = 8
 };
-enum AttnPlanError { ATTN_PLAN_OK = 0, ATTN_PLAN_KEY_SLOT = 1, ATTN_PLAN_O8 = 2, ATTN_PLAN_SPLIT_WS = 3, ATTN_PLAN_KEY_SLOT_BWD = 4 };
+enum AttnPlanError {
+  ATTN_PLAN_OK = 0, ATTN_PLAN_KEY_SLOT = 1, ATTN_PLAN_O8 = 2, ATTN_PLAN_SPLIT_WS = 3, ATTN_PLAN_KEY_SLOT_BWD = 4,
+  ATTN_PLAN_KSTART = 5
+};
 struct AttnPlan {
   int error = ATTN_PLAN_OK;
   int kernel = ATTN_NONE;
@@ -125,6 +128,7 @@ struct AttnPlan {
   int dt = 0;    // single-query kernel: tiles in flight per wave (3 / 2)
   int qp = 0;    // ... with the query projection in front (ca_decode_attn_qproj)
   int ks = 0;    // ... with the key_slot table
+  int km = 0;    // forward kernels: with a per-row first key (CaAttnDesc.kstart)
   unsigned grid = 0, block = 256;
   size_t lds = 0;  // dynamic LDS bytes
   // single-query kernel, key split: workgroups per (clip, head) at most, the split, byte offset of the partial slabs in
@@ -138,16 +142,23 @@ struct AttnBwdPlan {
   AttnPlan prep, dq, dkv;  // prep.kernel == ATTN_NONE: the wide dQ kernel produces D = rowsum(dO * O) itself
 };
 // one integer per instantiation: what the launchers switch over
-constexpr int attn_inst(int kernel, int hdpv, int drop, int wpe = 0, int dt = 0, int qp = 0, int ks = 0) {
-  return kernel << 16 | hdpv << 8 | drop << 7 | wpe << 5 | dt << 3 | qp << 1 | ks;
+// (km sits above the kernel id - hdpv << 8 reaches bit 15, the kernel ids bit 19 - so the numbers without it are the old ones)
+constexpr int attn_inst(int kernel, int hdpv, int drop, int wpe = 0, int dt = 0, int qp = 0, int ks = 0, int km = 0) {
+  return km << 24 | kernel << 16 | hdpv << 8 | drop << 7 | wpe << 5 | dt << 3 | qp << 1 | ks;
 }
-inline int attn_inst(const AttnPlan& p) { return attn_inst(p.kernel, p.hdpv, p.drop, p.wpe, p.dt, p.qp, p.ks); }
+inline int attn_inst(const AttnPlan& p) { return attn_inst(p.kernel, p.hdpv, p.drop, p.wpe, p.dt, p.qp, p.ks, p.km); }
 
 // cache rows by table: the single-query decode form only (attn_fwd_smallq_kernel<.., KS>)
 inline bool attn_key_slot_ok(const CaAttnDesc& d) {
   return d.key_slot == nullptr ||
          (d.Tq == 1 && d.klen != nullptr && d.hd <= ATTN_HD_NARROW && !d.causal && d.dropout_p == 0.f && d.O8 == nullptr &&
           d.split_ws == nullptr && d.row_off == nullptr && d.Tk <= ATTN_KEY_SLOT_MAX_KEYS);
+}
+// a per-row first key: the causal tiled forward and the single-query decode form, head_dim <= 64, the plain output only
+inline bool attn_kstart_ok(const CaAttnDesc& d) {
+  if (d.kstart == nullptr) return true;
+  if (d.hd > ATTN_HD_NARROW || d.dropout_p != 0.f || d.O8 || d.row_off || d.split_ws || d.key_slot) return false;
+  return d.causal || (d.Tq == 1 && d.klen != nullptr);
 }
 inline int attn_hdpv(const CaAttnDesc& d) { return d.hd <= ATTN_HD_NARROW ? 64 : 128; }
 inline unsigned attn_grid_of(const CaAttnDesc& d, int rows, int rows_per_tile) {
@@ -179,6 +190,7 @@ inline AttnPlan attn_plan_smallq(const CaAttnDesc& d, const AttnKnobs& k, int qp
   p.hdpv = 64;
   p.qp = qp;
   p.ks = d.key_slot ? 1 : 0;
+  p.km = d.kstart ? 1 : 0;
   const int bh = d.B * d.H;
   p.grid = (unsigned)bh;
   if (d.split_ws && d.Tk >= ATTN_SPLIT_MIN_KEYS) {
@@ -207,6 +219,7 @@ inline AttnPlan attn_plan_fwd(const CaAttnDesc& d, const AttnKnobs& k) {
   // 128-query workgroups when the query side fills them; CA_ATTN_WIDE=0 keeps the 64-query kernel
   const bool wide = k.wide && d.Tq >= ATTN_WIDE_MIN_ROWS;
   if (!attn_key_slot_ok(d)) p.error = ATTN_PLAN_KEY_SLOT;
+  else if (!attn_kstart_ok(d)) p.error = ATTN_PLAN_KSTART;
   else if (d.O8 && !(d.o8_scale && wide && (d.ldo % 8) == 0 && ((uintptr_t)d.O8 % 8) == 0)) p.error = ATTN_PLAN_O8;
   if (p.error) return p;
   const bool drop = d.dropout_p > 0.f;
@@ -215,17 +228,26 @@ inline AttnPlan attn_plan_fwd(const CaAttnDesc& d, const AttnKnobs& k) {
     return attn_plan_smallq(d, k, 0);
   // head_dim <= 64 without dropout: three workgroups per CU (see the kernel's header)
   attn_plan_query_side(p, d, wide, ATTN_FWD, ATTN_FWD_WIDE, k.wpe3);
+  p.km = d.kstart ? 1 : 0;
   return p;
 }
 
 // Greedy decoding: LayerNorm + query projection + single-query attention over a K|V cache in one launch per layer
 // (ca_decode_attn_qproj checks the descriptor itself: one query per clip, head_dim <= 64, no mask, no dropout).
-inline AttnPlan attn_plan_qproj(const CaAttnDesc& d, const AttnKnobs& k) { return attn_plan_smallq(d, k, 1); }
+inline AttnPlan attn_plan_qproj(const CaAttnDesc& d, const AttnKnobs& k) {
+  if (d.kstart) {  // the masked decoder self-attention takes its query from the projection GEMM
+    AttnPlan p;
+    p.error = ATTN_PLAN_KSTART;
+    return p;
+  }
+  return attn_plan_smallq(d, k, 1);
+}
 
 inline AttnBwdPlan attn_plan_bwd(const CaAttnDesc& d, const AttnKnobs& k) {
   AttnBwdPlan bp;
   if (!attn_key_slot_ok(d)) bp.error = ATTN_PLAN_KEY_SLOT;
   else if (d.key_slot) bp.error = ATTN_PLAN_KEY_SLOT_BWD;
+  else if (d.kstart) bp.error = ATTN_PLAN_KSTART;
   if (bp.error) return bp;
   const int hdpv = attn_hdpv(d), drop = d.dropout_p > 0.f ? 1 : 0;
   const bool narrow = d.hd <= ATTN_HD_NARROW;

@@ -79,7 +79,8 @@ def transcribe(model, processor, arrays: list, batch_size: int = 16, chunk_lengt
 
 def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max_length: int | None = None,
                        num_beams: int = 1, return_timestamps: bool = False, temperature=None, logprob_threshold=None,
-                       compression_ratio_threshold=None, no_speech_threshold=None, sample_seed: int = 0):
+                       compression_ratio_threshold=None, no_speech_threshold=None, sample_seed: int = 0, prompt_ids=None,
+                       condition_on_prev_tokens=None, prompt_condition_type=None, prompt: str | None = None):
     """The Whisper branch of the ASR pipeline ($TF/pipelines/automatic_speech_recognition.py:345,529,600): pad / trim
     every clip to 30 s, log-mel on the GPU, `model.generate(input_features, language="danish", task="transcribe")`
     (R/src/coral/evaluate.py:56-60), decode the generated ids without special tokens.
@@ -97,8 +98,22 @@ def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max
     transformers' temperature fallback (coral_amd/longform_whisper.py `FallbackPolicy`): every clip then takes the window
     loop; a window that fails a threshold is decoded again with sampling at the next temperature (uniforms from a CPU
     generator seeded with sample_seed), one that is silence is skipped; with return_timestamps every chunk's window
-    carries avg_logprob, temperature and no_speech_prob under "windows".  Not with beams, not with "word"."""
+    carries avg_logprob, temperature and no_speech_prob under "windows".  Not with beams, not with "word".
+    prompt_ids, condition_on_prev_tokens, prompt_condition_type: transformers' arguments of those names
+    (coral_amd/longform_whisper.py `PromptPolicy`): every clip then takes the window loop, and a window's decoder input
+    starts with the clip's text so far and / or the prompt, left-padded over the round's windows.  prompt: a string in
+    place of prompt_ids, through the processor's (or its tokenizer's) `get_prompt_ids`.  With the fallback arguments a
+    window accepted at a temperature of 0.5 or more leaves the next one unconditioned.  Not with beams, not with "word"."""
     model.eval()
+    if prompt is not None:
+        getter = getattr(processor, "get_prompt_ids", None) or getattr(getattr(processor, "tokenizer", None), "get_prompt_ids", None)
+        if prompt_ids is not None:
+            raise ValueError("prompt= and prompt_ids= name the same thing: pass one of them")
+        if getter is None:
+            raise ValueError("prompt=: this processor's tokenizer has no get_prompt_ids (the byte-level BPE files are not "
+                             "loaded); pass prompt_ids=, the ids transformers' get_prompt_ids returns for the string")
+        prompt_ids = [int(t) for t in getter(prompt)]
+    prompting = model.prompt_policy(prompt_ids, condition_on_prev_tokens, prompt_condition_type)
     policy = model.fallback_policy(temperature, logprob_threshold, compression_ratio_threshold, no_speech_threshold,
                                    sample_seed)
     texts, rows = [], []
@@ -117,7 +132,14 @@ def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max
                              "no_speech_threshold are not implemented with beam search")
         if word:
             raise ValueError("return_timestamps=\"word\" is not implemented with temperature fallback")
-    looped = [i for i, a in enumerate(arrays) if return_timestamps or policy is not None or len(a) > N_SAMPLES]
+    if prompting is not None:
+        if num_beams > 1:
+            raise ValueError(f"num_beams={num_beams}: prompt_ids / condition_on_prev_tokens / prompt_condition_type are not "
+                             "implemented with beam search")
+        if word:
+            raise ValueError("return_timestamps=\"word\" is not implemented with prompt_ids / condition_on_prev_tokens")
+    looped = [i for i, a in enumerate(arrays)
+              if return_timestamps or policy is not None or prompting is not None or len(a) > N_SAMPLES]
     if looped and num_beams > 1:
         raise ValueError(f"num_beams={num_beams}: return_timestamps / recordings longer than 30 s are decoded greedily "
                          "only (beam search with timestamps is not implemented)")
@@ -140,16 +162,18 @@ def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max
     for i, t, r in zip(plain, texts, rows):
         results[i], all_rows[i] = t, r
     timed, timed_rows = _transcribe_whisper_windows(model, processor, [arrays[i] for i in looped], batch_size, max_length,
-                                                    "word" if word else bool(return_timestamps), policy)
+                                                    "word" if word else bool(return_timestamps), policy, prompting)
     for i, t, r in zip(looped, timed, timed_rows):
         results[i], all_rows[i] = t, r
     return results, all_rows
 
 
-def _transcribe_whisper_windows(model, processor, arrays, batch_size, max_length, return_timestamps, policy=None):
+def _transcribe_whisper_windows(model, processor, arrays, batch_size, max_length, return_timestamps, policy=None,
+                                prompting=None):
     """The long-form loop over `arrays` (clips above 30 s, or every clip when timestamps are asked for), all of them
     sharing its rounds.  -> (texts, or {"text", "chunks"} per clip with return_timestamps; id rows).
-    return_timestamps="word": one chunk per word from the windows' token times."""
+    return_timestamps="word": one chunk per word from the windows' token times.  prompting: a PromptPolicy; the loop then
+    hands every call the decoder inputs of its windows."""
     from .longform_whisper import run_longform, stitched_ids
     from .whisper import N_SAMPLES
     from .whisper_align import cap_token_times, offline_decode, word_chunks
@@ -165,9 +189,11 @@ def _transcribe_whisper_windows(model, processor, arrays, batch_size, max_length
     # transformers' does for a clip of one window; the DTW of a window sees only what is left of the true frames
     true_frames = [min(m.shape[1], max(1, len(a) // 160)) for m, a in zip(mels, arrays)]
 
-    def window_generate(batch):
+    def window_generate(batch, inputs=None):
         feats = torch.stack([torch.nn.functional.pad(mels[c][:, seek:seek + 3000], (0, max(0, 3000 - (mels[c].shape[1] - seek))))
                              for c, seek in batch])
+        if inputs is not None:
+            return model.prompted_window(feats, inputs, True)
         if word:  # (num_frames = min(3000, true frames left): the padding behind them never enters the DTW)
             return model.generate(feats, language="danish", task="transcribe", max_length=max_length, return_timestamps=True,
                                   return_token_timestamps=True,
@@ -178,15 +204,19 @@ def _transcribe_whisper_windows(model, processor, arrays, batch_size, max_length
     if policy is not None:
         attempt = model.fallback_attempts(policy, max_length, True)
 
-        def window_generate(batch, temperature, uniforms):  # noqa: F811  (the protocol under a policy)
+        def window_generate(batch, temperature, uniforms, inputs=None):  # noqa: F811  (the protocol under a policy)
             feats = {(c, seek): torch.nn.functional.pad(mels[c][:, seek:seek + 3000],
                                                         (0, max(0, 3000 - (mels[c].shape[1] - seek)))) for c, seek in batch}
-            return attempt(batch, temperature, uniforms, feats)
+            return attempt(batch, temperature, uniforms, feats, inputs)
 
+    extra = {}
+    if prompting is not None:
+        extra = dict(conditioning=prompting, init_tokens=model.forced_prefix(return_timestamps=True),
+                     max_target_positions=s.max_target_positions)
     done = run_longform(window_generate, [m.shape[1] for m in mels], tb, prefix_len, s.pad_token_id, s.eos_token_id,
                         batch_size=batch_size, return_token_timestamps=word, fallback=policy,
                         vocab_size=s.vocab_size if policy is not None else None,
-                        max_length=max_length if policy is not None else None)
+                        max_length=max_length if policy is not None or prompting is not None else None, **extra)
     tok = getattr(processor, "tokenizer", None)
     decode = offline_decode if tok is None else (lambda ids: tok.decode([int(t) for t in ids], skip_special_tokens=False))
     results, rows = [], []
@@ -218,6 +248,11 @@ def _whisper_timestamp_mode(value):
 def _plain(value):
     """A temperature from the configuration: a number, None, or a list of numbers as a tuple."""
     return value if value is None or isinstance(value, (int, float)) else tuple(float(t) for t in value)
+
+
+def _ids(value):
+    """prompt_ids from the configuration: None or a list of ids."""
+    return None if value is None else [int(t) for t in value]
 
 
 def saved_model_type(model_dir) -> str:
@@ -272,7 +307,10 @@ def evaluate(config, examples: list | None = None) -> dict:
                                             logprob_threshold=config.get("logprob_threshold", None),
                                             compression_ratio_threshold=config.get("compression_ratio_threshold", None),
                                             no_speech_threshold=config.get("no_speech_threshold", None),
-                                            sample_seed=int(config.get("sample_seed", 0) or 0))
+                                            sample_seed=int(config.get("sample_seed", 0) or 0),
+                                            prompt_ids=_ids(config.get("prompt_ids", None)),
+                                            condition_on_prev_tokens=bool(config.get("condition_on_prev_tokens", False) or False),
+                                            prompt_condition_type=config.get("prompt_condition_type", None))
         if preds and isinstance(preds[0], dict):
             timed, preds = preds, [p["text"] for p in preds]
     else:

@@ -922,8 +922,9 @@ def prof_end():
 
 def _attn_desc(Q, K, V, O, lse, *, B, H, Tq, Tk, hd, Tqp, scale, ldq, ldk, ldv, ldo, sqb, skb, svb, sob,
                q_off=0, k_off=0, v_off=0, o_off=0, klen=None, causal=False, dropout_p=0.0, dropout_seed=0,
-               O8=None, o8_scale=None, o8_amax=None, split_ws=None, row_off=None, key_slot=None):
+               O8=None, o8_scale=None, o8_amax=None, split_ws=None, row_off=None, key_slot=None, kstart=None):
     d = CaAttnDesc()
+    d.kstart = _p(kstart)  # forward: int32 [B], the first key of every row (left-padded decoder prompts); None = 0
     d.key_slot = _p(key_slot)  # Tq = 1 decode form: int32 [B, Tk], the cache row of every key (beam search)
     d.row_off = _p(row_off)  # packed rows: utterance b at rows row_off[b] .. row_off[b + 1] (Tq = Tk = the longest)
     if split_ws is not None:  # key split of the small-query kernel (attn_split_workspace)

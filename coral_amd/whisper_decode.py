@@ -75,9 +75,18 @@ class DecodeRequest(NamedTuple):  # what `generate`'s arguments ask for, checked
 def check_generate_arguments(s, input_features, prefix, max_length, use_cache, use_graph, num_beams, length_penalty,
                              early_stopping, return_trace, _beam_path, return_timestamps, timestamp_begin,
                              max_initial_timestamp_index, return_token_timestamps, alignment_heads, temperature,
-                             sample_uniforms, return_stats, no_speech_token, cross_kv) -> DecodeRequest:
+                             sample_uniforms, return_stats, no_speech_token, cross_kv, prefix_rows=None,
+                             prefix_start=None, no_speech_index=0) -> DecodeRequest:
     """Every refusal of `generate`, before any device work (s: the WhisperShape)."""
     beam = num_beams != 1 or _beam_path
+    if prefix_rows is not None:
+        check_prefix_rows(s, prefix, prefix_rows, prefix_start, max_length, use_cache, num_beams, _beam_path,
+                          return_token_timestamps)
+        prefix = [s.pad_token_id] * int(prefix_rows.shape[1])  # (below only its length is looked at)
+    elif prefix_start is not None:
+        raise ValueError("prefix_start= comes with prefix_rows=")
+    if not isinstance(no_speech_index, int) or not 0 <= no_speech_index < len(prefix):
+        raise ValueError(f"no_speech_index={no_speech_index!r} lies outside the {len(prefix)} prefix positions")
     ts = None
     scoring = None
     if temperature is None or not isinstance(temperature, (int, float)) or isinstance(temperature, bool) \
@@ -138,6 +147,38 @@ def check_generate_arguments(s, input_features, prefix, max_length, use_cache, u
     return DecodeRequest(beam, ts, scoring, alignment_heads if return_token_timestamps else None)
 
 
+def check_prefix_rows(s, prefix, prefix_rows, prefix_start, max_length, use_cache, num_beams, beam_path,
+                      return_token_timestamps) -> None:
+    """The limits of generate(prefix_rows=, prefix_start=): left-padded decoder inputs, one row per clip."""
+    if prefix is not None:
+        raise ValueError("prefix_rows= replaces prefix=: pass prefix=None with it")
+    if not isinstance(prefix_rows, torch.Tensor) or prefix_rows.dim() != 2 or prefix_rows.dtype != torch.int64 \
+            or prefix_rows.shape[1] < 1:
+        raise ValueError("prefix_rows must be an int64 tensor [clips, P] with P >= 1")
+    B, P = prefix_rows.shape
+    if not isinstance(prefix_start, torch.Tensor) or prefix_start.dtype != torch.int32 or tuple(prefix_start.shape) != (B,):
+        raise ValueError(f"prefix_rows needs prefix_start, int32 [{B}]: the number of leading pad positions of every row")
+    if num_beams != 1 or beam_path:
+        raise ValueError(f"generate(num_beams={num_beams}): prefix_rows is not implemented with beam search")
+    if return_token_timestamps:
+        raise ValueError("prefix_rows is not implemented with return_token_timestamps=True")
+    if not use_cache:
+        raise ValueError("prefix_rows needs use_cache=True (the pass without a cache knows no left padding)")
+    if P >= max_length or max_length > s.max_target_positions:
+        raise ValueError(f"prefix_rows needs P < max_length <= {s.max_target_positions}, got P = {P}, max_length = "
+                         f"{max_length}")
+    start = prefix_start.cpu()
+    if int(start.min()) < 0 or int(start.max()) >= P:
+        raise ValueError(f"prefix_start must lie in [0, P = {P}): every row keeps at least one token")
+    rows = prefix_rows.cpu()
+    if int(rows.min()) < 0 or int(rows.max()) >= s.vocab_size:
+        raise ValueError("prefix_rows holds ids outside the vocabulary")
+    valid = torch.arange(P)[None, :] >= start[:, None].long()
+    if bool(((rows == s.pad_token_id) & valid).any()):
+        raise ValueError(f"prefix_rows: pad id {s.pad_token_id} inside a row's valid part.  transformers masks decoder "
+                         "inputs by value (ids != pad_token_id); only the left run of padding it produces is supported")
+
+
 @functools.lru_cache(maxsize=None)
 def decoder_layer_names(l: int) -> dict:
     """The parameters of decoder layer l, HF names under the field names of `CaDecodeLayer` (its parameter fields, in its
@@ -166,9 +207,11 @@ class WhisperDecoding:
         return dict(kv=[torch.zeros(B * max_len * 2 * d, dtype=torch.bfloat16, device=self.device)
                         for _ in range(self.s.decoder_layers)], max_len=max_len, pos=0, B=B)
 
-    def _prefill_self_attn(self, l, h0, h1, w, ckv, B, n, pos0, Lmax):
+    def _prefill_self_attn(self, l, h0, h1, w, ckv, B, n, pos0, Lmax, kstart=None, klen=None):
         """The self-attention half of layer l for n new tokens per clip at the HOST-side position pos0 (h0 -> h1): unlike
-        the token step's, K|V go into the cache rows pos0.. of every clip by a batched GEMM and the attention is causal."""
+        the token step's, K|V go into the cache rows pos0.. of every clip by a batched GEMM and the attention is causal.
+        kstart (int32 [B] on the device, or None): the first key of every row - the left padding of `prefix_rows`
+        (CaAttnDesc.kstart); a single token then comes with klen = pos0 + 1 per row, the single-query form's key count."""
         s, st = self.s, self.store
         p32, p16, o = st.p32, st.p16, st.off
         d, H, M = s.d_model, s.decoder_attention_heads, B * n
@@ -182,14 +225,16 @@ class WhisperDecoding:
                  bias_off=o(nm["bkv"]), batch2=B, sA=(0, n * d), sC=(0, Lmax * 2 * d))
         ops.attn_fwd(q, ckv, ckv, ctx, lse, B=B, H=H, Tq=n, Tk=pos0 + n, hd=hd, Tqp=w["ca"]["Tqp"],
                      scale=hd ** -0.5, ldq=d, ldk=2 * d, ldv=2 * d, ldo=d, sqb=n * d, skb=Lmax * 2 * d,
-                     svb=Lmax * 2 * d, sob=n * d, k_off=0, v_off=d, causal=(n > 1))
+                     svb=Lmax * 2 * d, sob=n * d, k_off=0, v_off=d, causal=(n > 1), kstart=kstart, klen=klen)
         ops.gemm(ctx, p16, h1, M=M, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(nm["wo"]), bias=p32, bias_off=o(nm["bo"]),
                  epilogue=EPI_RESIDUAL, R=h0, ldr=d)
 
-    def decode_step(self, new_ids: torch.Tensor, cross_kv: list, cache: dict) -> torch.Tensor:
+    def decode_step(self, new_ids: torch.Tensor, cross_kv: list, cache: dict, kstart=None) -> torch.Tensor:
         """Feed `new_ids` [B, n] (the forced prefix at position 0, then one token per call) through the
         decoder, appending their K|V to `cache`; returns fp32 logits [B, V] of the last position.
-        Same arithmetic as `decode(...)[:, -1]`: each new query attends to all cached keys."""
+        Same arithmetic as `decode(...)[:, -1]`: each new query attends to all cached keys.
+        kstart (int32 [B] on the device): cache positions in front of kstart[b] are left padding, attended to by no query
+        of clip b.  Positions count the padding, as in transformers (`WhisperDecoder.forward`: arange over the padded row)."""
         self._await_all()
         s, dev = self.s, self.device
         B, n = new_ids.shape
@@ -204,8 +249,9 @@ class WhisperDecoding:
         pos = (torch.arange(n, dtype=torch.int32, device=dev) + pos0).repeat(B)
         h0, h1 = w["h"]
         self._embed(ids, pos, h0, M)
+        klen = torch.full((B,), pos0 + 1, dtype=torch.int32, device=dev) if kstart is not None and n == 1 else None
         for l, (_, ca, ff) in enumerate(self.dec_blocks):
-            self._prefill_self_attn(l, h0, h1, w, cache["kv"][l], B, n, pos0, Lmax)
+            self._prefill_self_attn(l, h0, h1, w, cache["kv"][l], B, n, pos0, Lmax, kstart, klen)
             ca.forward(h1, h0, w["ca"], B, n, Te, kv=cross_kv[l])
             ff.forward(h0, h1, w["ff"], M)
             h0, h1 = h1, h0
@@ -214,24 +260,29 @@ class WhisperDecoding:
         return logits[:, :s.vocab_size]
 
     # ---- one-token step with static shapes and pointers (capturable in a HIP graph) -----------------
-    def _graph_state(self, cache: dict, cross_kv: list, pad_id: int, eos_id: int):
+    def _graph_state(self, cache: dict, cross_kv: list, pad_id: int, eos_id: int, kstart=None):
         """Static buffers of the per-token step: everything that changes from token to token (position,
         cached length, token ids, finished flags) lives in device memory, so the launch sequence is
-        identical for every token and can be replayed as one graph."""
+        identical for every token and can be replayed as one graph.  kstart (int32 [B] on the device, or None): the first
+        key of every row, which does not change from token to token."""
         B, Lmax, dev = cache["B"], cache["max_len"], self.device
         i32 = lambda: torch.zeros(B, dtype=torch.int32, device=dev)  # noqa: E731
         return dict(tok=i32(), pos=i32(), klen=i32(), nxt=i32(), done=torch.zeros(B, dtype=torch.bool, device=dev),
                     out=torch.full((B, Lmax), pad_id, dtype=torch.int64, device=dev),
                     logits=torch.zeros(B, _r8(self.s.vocab_size), dtype=torch.float32, device=dev),
-                    pad_id=pad_id, eos=eos_id, cross=cross_kv)
+                    pad_id=pad_id, eos=eos_id, cross=cross_kv, kstart=kstart)
 
     def _persistent_state(self, cache: dict, g: dict, suppress: torch.Tensor):
         """Descriptor + device tables of ca_whisper_decode_token for this decode state, or None where the launch
         sequence stays (shape / device outside the kernel's limits, CA_DECODE_PERSISTENT=0).  Decoding with timestamps
         (g["ts"]) always keeps the launch sequence: the one-launch kernel's pick is the plain masked argmax
-        (csrc/decode.hip), the timestamp rules live in ca_argmax_timestamps_advance."""
+        (csrc/decode.hip), the timestamp rules live in ca_argmax_timestamps_advance.  So does decoding from left-padded
+        prefix rows (g["kstart"]): the one-launch kernel's self-attention knows no first key."""
         if "persist" in g:
             return g["persist"]
+        if g.get("kstart") is not None:
+            g["persist"] = None
+            return None
         if g.get("ts") is not None or g.get("scored") is not None:  # (the scored pick is a launch of its own as well)
             g["persist"] = None
             return None
@@ -290,9 +341,10 @@ class WhisperDecoding:
     def _decode_rows(self, cache: dict, g: dict, R: int, key_slot=None, cross=None, may_fuse: bool = True):
         """One token per row, g["tok"] at position g["pos"] (both in device memory), through the decoder against the
         self-attention cache: ~7 launches per layer, the R rows' logits into g["logits"].  A row's K|V go to cache row
-        r * max_len + pos[r]; it attends to g["klen"][r] keys of its own cache row, or with key_slot (int32 [R, max_len])
-        to the cache rows that table names.  cross = (B, Tq, split_ws): the cross-attention's view of the R = B * Tq rows as
-        Tq queries of each of B clips and its key-split workspace; default (R, 1, the decoder workspace's).  may_fuse:
+        r * max_len + pos[r]; it attends to g["klen"][r] keys of its own cache row - from key g["kstart"][r] on, where the
+        state has one - or with key_slot (int32 [R, max_len]) to the cache rows that table names.  cross = (B, Tq,
+        split_ws): the cross-attention's view of the R = B * Tq rows as Tq queries of each of B clips and its key-split
+        workspace; default (R, 1, the decoder workspace's).  may_fuse:
         whether LayerNorm + q projection + cross-attention may run as one launch (Tq = 1 only)."""
         s, st = self.s, self.store
         p32, p16, o = st.p32, st.p16, st.off
@@ -329,7 +381,7 @@ class WhisperDecoding:
                      a_ln=(*ln1, eps) if ln_in else None)
             ops.attn_fwd(q, ckv, ckv, ctx, lse, B=R, H=H, Tq=1, Tk=Lmax, hd=hd, Tqp=32, scale=hd ** -0.5, ldq=d, ldk=2 * d,
                          ldv=2 * d, ldo=d, sqb=d, skb=Lmax * 2 * d, svb=Lmax * 2 * d, sob=d, k_off=0, v_off=d,
-                         klen=g["klen"], key_slot=key_slot)
+                         klen=g["klen"], key_slot=key_slot, kstart=g.get("kstart"))
             ops.gemm(ctx, p16, h1, M=R, N=d, K=d, lda=d, ldb=d, ldc=d, b_off=o(nm["wo"]), bias=p32, bias_off=o(nm["bo"]),
                      epilogue=EPI_RESIDUAL, R=h0, ldr=d)
             if fused:
@@ -437,7 +489,8 @@ class WhisperDecoding:
                  _beam_path: bool = False, return_timestamps: bool = False, timestamp_begin: int | None = None,
                  max_initial_timestamp_index: int | None = None, return_token_timestamps: bool = False,
                  alignment_heads=None, num_frames=None, median_filter_width: int = 7, temperature: float = 0.0,
-                 sample_uniforms=None, return_stats: bool = False, no_speech_token: int | None = None, cross_kv=None):
+                 sample_uniforms=None, return_stats: bool = False, no_speech_token: int | None = None, cross_kv=None,
+                 prefix_rows=None, prefix_start=None, no_speech_index: int = 0):
         """Greedy decoding with a forced prefix (<|sot|><|da|><|transcribe|><|notimestamps|> in CoRal's
         evaluation): masked argmax on the GPU (ca_argmax_masked), stop at EOS / max_length.
         num_beams = k >= 2: beam search (`_generate_beam`; length_penalty, early_stopping True / False as in
@@ -455,13 +508,25 @@ class WhisperDecoding:
         under the processed distribution at temperature 1 and their count; with `no_speech_token`, the probability of that
         id at the first prefix position.  Either keeps the launch sequence (graph-captured per token); not with beams.
         cross_kv: the result of `cross_kv(encode(...))` (or `gather_cross_kv` of it) - the encoder is then not run and
-        input_features may be None."""
+        input_features may be None.
+        prefix_rows (with prefix=None): int64 [B, P], a decoder input row per clip - previous text or a prompt in front of
+        the forced prefix, as `_prepare_decoder_input_ids` of transformers' long-form loop builds them - LEFT-padded with
+        the pad id; prefix_start int32 [B]: the number of leading pad positions of every row.  The padding is attended to
+        by nothing (CaAttnDesc.kstart) and counts as positions, as in transformers; the timestamp rules begin at P; the
+        returned rows start with the P columns given.  Greedy or sampled, with or without timestamps; not with beams or
+        token timestamps; the one-launch-per-token kernel is bypassed.  no_speech_index: the prefix position whose logits
+        give the no-speech probability (<|startoftranscript|>: P minus the forced tokens)."""
         s, dev = self.s, self.device
         req = check_generate_arguments(
             s, input_features, prefix, max_length, use_cache, use_graph, num_beams, length_penalty, early_stopping,
             return_trace, _beam_path, return_timestamps, timestamp_begin, max_initial_timestamp_index,
-            return_token_timestamps, alignment_heads, temperature, sample_uniforms, return_stats, no_speech_token, cross_kv)
+            return_token_timestamps, alignment_heads, temperature, sample_uniforms, return_stats, no_speech_token, cross_kv,
+            prefix_rows, prefix_start, no_speech_index)
         ts = req.ts
+        rows0 = kstart = None  # left-padded prefix rows on the device and their first keys; None wherever no prompt is in play
+        if prefix_rows is not None:
+            rows0, kstart = prefix_rows.to(dev).contiguous(), prefix_start.to(dev).contiguous()
+            prefix = [s.pad_token_id] * rows0.shape[1]  # (a stand-in where only the length P is looked at)
         if cross_kv is not None:
             kv, enc = cross_kv, None
             B = kv[0].numel() // (s.max_source_positions * 2 * s.d_model)
@@ -482,26 +547,29 @@ class WhisperDecoding:
                 return rows
             return rows, self.token_timestamps(rows, kv, len(prefix), req.alignment_heads, num_frames, median_filter_width)
 
+        if rows0 is not None and rows0.shape[0] != B:
+            raise ValueError(f"prefix_rows has {rows0.shape[0]} rows for {B} clips")
         if req.beam:
             return self._generate_beam(kv, prefix, max_length, sup, sup_begin, num_beams, float(length_penalty),
                                        bool(early_stopping), return_trace, use_graph)
         if req.scoring is not None:
             if temperature > 0 and sample_uniforms.shape[0] != B:
                 raise ValueError(f"sample_uniforms has {sample_uniforms.shape[0]} rows for {B} clips")
-            rows, sc = self._generate_graph(kv, prefix, max_length, sup, sup_begin, ts, req.scoring)
+            rows, sc = self._generate_graph(kv, prefix, max_length, sup, sup_begin, ts, req.scoring, rows0, kstart,
+                                            no_speech_index)
             stats = dict(sum_logprob=sc["sum_logprob"].cpu().tolist(), n_scored=sc["n_scored"].cpu().tolist(),
                          no_speech_prob=sc["no_speech_prob"].cpu().tolist() if no_speech_token is not None else None)
             return (rows, stats) if return_stats else rows
         if use_cache and use_graph and max_length > len(prefix) + 2:
-            return with_times(self._generate_graph(kv, prefix, max_length, sup, sup_begin, ts)[0])
-        ids = torch.tensor([prefix] * B, dtype=torch.int64, device=dev)
+            return with_times(self._generate_graph(kv, prefix, max_length, sup, sup_begin, ts, None, rows0, kstart)[0])
+        ids = torch.tensor([prefix] * B, dtype=torch.int64, device=dev) if rows0 is None else rows0
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         nxt = torch.empty(B, dtype=torch.int32, device=dev)
         cache = self.new_decode_cache(B, max_length) if use_cache else None
         feed = ids
         while ids.shape[1] < max_length and not bool(done.all()):
             if use_cache:
-                base = self.decode_step(feed, kv, cache).contiguous()  # fp32 [B, V]
+                base = self.decode_step(feed, kv, cache, kstart).contiguous()  # fp32 [B, V]
             else:
                 base = self.decode(ids, enc, kv, last_only=True)[:, 0, :].contiguous()
             mask = sup_begin if ids.shape[1] == len(prefix) else sup
@@ -587,18 +655,21 @@ class WhisperDecoding:
         return [c.view(-1, n).index_select(0, idx).reshape(-1) for c in kv]
 
     # ---- greedy search on the cache --------------------------------------------------------------------------------------
-    def _generate_graph(self, kv, prefix, max_length, sup, sup_begin, ts=None, scoring: Scoring | None = None):
+    def _generate_graph(self, kv, prefix, max_length, sup, sup_begin, ts=None, scoring: Scoring | None = None,
+                        prefix_rows=None, kstart=None, no_speech_index: int = 0):
         """Greedy loop with the per-token step captured once in a HIP graph and replayed: the ~350 small
         launches of a token (24-32 layers x 14 kernels) cost one graph launch instead of 350 host calls.
-        -> (id rows, the scored pick's state or None: dict(sum_logprob, n_scored, no_speech_prob, ...) on the device)."""
+        -> (id rows, the scored pick's state or None: dict(sum_logprob, n_scored, no_speech_prob, ...) on the device).
+        prefix_rows int64 [B, P] / kstart int32 [B], both on the device: a left-padded row per clip in place of `prefix`
+        (then only P long) and its first key - a static array, so the per-token graph replays unchanged."""
         s, dev = self.s, self.device
         B, V, P = kv[0].shape[0] // (s.max_source_positions * 2 * s.d_model), s.vocab_size, len(prefix)
         cache = self.new_decode_cache(B, max_length)
-        g = self._graph_state(cache, kv, s.pad_token_id, s.eos_token_id)
+        g = self._graph_state(cache, kv, s.pad_token_id, s.eos_token_id, kstart)
         g["ts"] = ts  # (begin_index, timestamp_begin, max_initial_timestamp_index) or None
         # the forced prefix and the first free token run eagerly (different shapes / begin-suppress mask)
-        ids0 = torch.tensor([prefix] * B, dtype=torch.int64, device=dev)
-        base = self.decode_step(ids0, kv, cache).contiguous()
+        ids0 = torch.tensor([prefix] * B, dtype=torch.int64, device=dev) if prefix_rows is None else prefix_rows
+        base = self.decode_step(ids0, kv, cache, kstart).contiguous()
         if scoring is not None:
             g["scored"] = sc = dict(inv_t=scoring.inv_t, uniforms=scoring.uniforms, no_speech_prob=None,
                                     sum_logprob=torch.zeros(B, dtype=torch.float32, device=dev),
@@ -607,8 +678,9 @@ class WhisperDecoding:
                 sc["uniforms"] = sc["uniforms"].to(dev, torch.float32).contiguous()
             if scoring.no_speech_token is not None:
                 # WhisperNoSpeechDetection: the softmax of the raw logits at the start-of-transcript position, i.e. the
-                # head on prefix position 0 (decode_step left the final LayerNorm of every prefix row in the workspace)
-                hf0 = self._decoder_ws(B, P)["hf"][:B * P * s.d_model].view(B, P, s.d_model)[:, 0, :].contiguous()
+                # head on prefix position 0 (decode_step left the final LayerNorm of every prefix row in the workspace);
+                # behind previous text or a prompt that token stands at no_speech_index
+                hf0 = self._decoder_ws(B, P)["hf"][:B * P * s.d_model].view(B, P, s.d_model)[:, no_speech_index, :].contiguous()
                 lg0 = self.head.project(hf0, B)
                 sc["no_speech_prob"] = torch.empty(B, dtype=torch.float32, device=dev)
                 ops.row_token_prob(lg0, sc["no_speech_prob"], B, V, _r8(V), scoring.no_speech_token)
@@ -636,7 +708,8 @@ class WhisperDecoding:
                 warnings.warn("coral_amd: " + msg + "; decoding this batch again as a launch sequence and keeping that "
                               "path for this engine (CA_DECODE_STRICT=1 raises instead)")
                 self._persistent_off = True
-                return self._generate_graph(kv, prefix, max_length, sup, sup_begin, ts, scoring)
+                return self._generate_graph(kv, prefix, max_length, sup, sup_begin, ts, scoring, prefix_rows, kstart,
+                                            no_speech_index)
         # trim like the eager loop: stop at the first column where every row had already finished
         fin = (out == s.eos_token_id).cumsum(1) > 0
         allfin = fin.all(0)

@@ -237,7 +237,8 @@ class WhisperForConditionalGeneration:
                  length_penalty: float = 1.0, early_stopping=False, return_timestamps: bool | None = False,
                  return_token_timestamps: bool | None = False, num_frames=None, temperature=None, logprob_threshold=None,
                  compression_ratio_threshold=None, no_speech_threshold=None, sample_seed: int = 0,
-                 return_fallback_stats: bool = False, **other):
+                 return_fallback_stats: bool = False, prompt_ids=None, condition_on_prev_tokens=None,
+                 prompt_condition_type=None, **other):
         """Greedy (num_beams 1 / None: other keyword arguments are ignored, as before) or beam search (num_beams >= 2,
         transformers' semantics; every generation argument this build does not implement is then refused by name).
         return_timestamps=True (greedy only): the prefix drops <|notimestamps|> and every pick obeys Whisper's timestamp
@@ -249,13 +250,30 @@ class WhisperForConditionalGeneration:
         no_speech_threshold, sample_seed: transformers' temperature fallback for clips of one window (greedy only, no token
         timestamps): `decode_with_fallback` of coral_amd/longform_whisper.py with one window per clip, the encoder run once.
         A clip skipped as silence comes back as the prefix and EOS.  return_fallback_stats=True: -> (ids, per clip
-        dict(temperature, avg_logprob, compression_ratio, no_speech_prob, skipped))."""
+        dict(temperature, avg_logprob, compression_ratio, no_speech_prob, skipped)).
+        prompt_ids (the ids `get_prompt_ids` returns, <|startofprev|> first), condition_on_prev_tokens,
+        prompt_condition_type: transformers' arguments of the same names (coral_amd/longform_whisper.py `PromptPolicy`).
+        Here every clip is one window, so what they change is the decoder input in front of the forced prefix: the
+        prompt (behind a mask when conditioning is on, as `_prepare_decoder_input_ids` builds it); max_length grows by
+        its length as `_set_max_new_tokens_and_length` grows it.  The rows returned start with the forced prefix, the
+        prompt is stripped.  Greedy only, not with token timestamps or the fallback arguments (`transcribe_whisper`
+        takes all of them together, and recordings of any length)."""
         if language not in ("danish", "da") or task != "transcribe":
             raise ValueError("only language='danish', task='transcribe' (CoRal's evaluation call) is wired up")
         prefix = self.forced_prefix()
         num_beams = 1 if num_beams is None else num_beams
         kw = {}
         policy = None
+        prompting = self.prompt_policy(prompt_ids, condition_on_prev_tokens, prompt_condition_type)
+        if prompting is not None:
+            if num_beams != 1:
+                raise ValueError(f"generate(num_beams={num_beams}): prompt_ids / condition_on_prev_tokens / "
+                                 "prompt_condition_type are not implemented with beam search")
+            if return_token_timestamps:
+                raise ValueError("prompt_ids / condition_on_prev_tokens are not implemented with return_token_timestamps=True")
+            if self.fallback_policy(temperature, logprob_threshold, compression_ratio_threshold, no_speech_threshold) is not None:
+                raise ValueError("prompt_ids / condition_on_prev_tokens together with temperature fallback: "
+                                 "coral_amd.evaluate.transcribe_whisper runs the two in one loop, generate() does not")
         if num_beams != 1:  # with beams they are refused by name below, their neutral values pass as before
             given = dict(temperature=temperature, logprob_threshold=logprob_threshold,
                          compression_ratio_threshold=compression_ratio_threshold, no_speech_threshold=no_speech_threshold)
@@ -290,6 +308,17 @@ class WhisperForConditionalGeneration:
             check_beam_arguments(int(input_features.shape[0]), num_beams, length_penalty, early_stopping, other)
             kw = dict(num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping)
         # CoRal clears `suppress_tokens`; the default begin-suppress set (blank ' ' = 220, eos) stays
+        if prompting is not None:
+            from .longform_whisper import grown_max_length, prepare_decoder_inputs
+
+            s, n = self.shape, int(input_features.shape[0])
+            rows, start, masked = prepare_decoder_inputs(prefix, prompting.first_segments(n), list(range(n)),
+                                                         [prompting.condition_on_prev_tokens] * n, prompting, s.pad_token_id,
+                                                         s.max_target_positions, self.forced_prefix()[-1] + 1)
+            inputs = dict(rows=rows, start=start, masked=masked,
+                          max_length=grown_max_length(max_length, len(rows[0]), s.max_target_positions))
+            out = self.prompted_window(input_features, inputs, bool(return_timestamps))
+            return [list(prefix) + [int(t) for t in r[len(rows[0]):]] for r in out]
         if policy is not None:
             from .longform_whisper import decode_with_fallback
 
@@ -309,6 +338,34 @@ class WhisperForConditionalGeneration:
         return self.engine.generate(input_features, prefix, max_length, suppress_tokens=None,
                                     begin_suppress_tokens=[220, self.shape.eos_token_id], **kw)
 
+    def prompt_policy(self, prompt_ids=None, condition_on_prev_tokens=None, prompt_condition_type=None):
+        """The PromptPolicy of these generate arguments, or None where they leave decoding as it is.  <|startofprev|> is
+        the generation config's prev_sot_token_id (CoRal clears suppress_tokens, transformers' other source of it); without
+        it previous text stands in front of the forced prefix with no token before it, as in transformers."""
+        from .longform_whisper import PromptPolicy
+
+        if prompt_ids is None and not condition_on_prev_tokens and prompt_condition_type is None:
+            return None
+        if prompt_ids is not None:
+            prompt_ids = tuple(int(t) for t in (prompt_ids.tolist() if hasattr(prompt_ids, "tolist") else prompt_ids))
+        prev = self.generation_config.get("prev_sot_token_id")
+        policy = PromptPolicy(prompt_ids, prompt_condition_type, bool(condition_on_prev_tokens), None if prev is None else int(prev))
+        return policy if policy.active else None
+
+    def prompted_window(self, input_features, inputs: dict, return_timestamps: bool, cross_kv=None, **scoring):
+        """One batch of windows decoded from the decoder inputs of `prepare_decoder_inputs` / `run_longform` (dict(rows,
+        start, max_length[, no_speech_index])): `engine.generate(prefix_rows=, prefix_start=)`.  -> what that returns."""
+        s = self.shape
+        kw = {}
+        if return_timestamps:
+            kw = dict(return_timestamps=True, timestamp_begin=self.forced_prefix()[-1] + 1,
+                      max_initial_timestamp_index=self.generation_config.get("max_initial_timestamp_index", None))
+        return self.engine.generate(input_features, None, int(inputs["max_length"]), suppress_tokens=None,
+                                    begin_suppress_tokens=[220, s.eos_token_id],
+                                    prefix_rows=torch.tensor(inputs["rows"], dtype=torch.int64),
+                                    prefix_start=torch.tensor(inputs["start"], dtype=torch.int32), cross_kv=cross_kv,
+                                    no_speech_index=int(inputs.get("no_speech_index", 0)), **kw, **scoring)
+
     def fallback_policy(self, temperature=None, logprob_threshold=None, compression_ratio_threshold=None,
                         no_speech_threshold=None, sample_seed: int = 0):
         """The FallbackPolicy of these generate arguments, or None where they leave decoding as it is (temperature None
@@ -324,9 +381,11 @@ class WhisperForConditionalGeneration:
                               self.forced_prefix()[-1] - 1 if no_speech_threshold is not None else None, int(sample_seed))
 
     def fallback_attempts(self, policy, max_length: int, return_timestamps: bool):
-        """-> attempt(batch, temperature, uniforms, feats): the `window_generate` of `decode_with_fallback` on this model.
-        batch: keys of `feats` (key -> log-mel [mels, 3000]).  The encoder and the cross K|V run when a batch brings keys
-        that the last encoded batch did not hold; a later attempt decodes its rows against a gather of that K|V."""
+        """-> attempt(batch, temperature, uniforms, feats[, inputs]): the `window_generate` of `decode_with_fallback` on this
+        model.  batch: keys of `feats` (key -> log-mel [mels, 3000]).  The encoder and the cross K|V run when a batch
+        brings keys that the last encoded batch did not hold; a later attempt decodes its rows against a gather of that
+        K|V.  inputs: the attempt's decoder inputs under a PromptPolicy (`run_longform(conditioning=)`), in place of the
+        forced prefix."""
         eng, s = self.engine, self.shape
         prefix = self.forced_prefix(return_timestamps)
         kw = {}
@@ -335,12 +394,15 @@ class WhisperForConditionalGeneration:
                       max_initial_timestamp_index=self.generation_config.get("max_initial_timestamp_index", None))
         held = dict(keys={}, kv=None)
 
-        def attempt(batch, temperature, uniforms, feats):
+        def attempt(batch, temperature, uniforms, feats, inputs=None):
             if held["kv"] is None or any(k not in held["keys"] for k in batch):
                 held["kv"] = eng.cross_kv(eng.encode(torch.stack([torch.as_tensor(feats[k]) for k in batch])))
                 held["keys"] = {k: i for i, k in enumerate(batch)}
             rows = [held["keys"][k] for k in batch]
             kv = held["kv"] if rows == list(range(len(held["keys"]))) else eng.gather_cross_kv(held["kv"], rows)
+            if inputs is not None:
+                return self.prompted_window(None, inputs, return_timestamps, cross_kv=kv, temperature=float(temperature),
+                                            sample_uniforms=uniforms, return_stats=True, no_speech_token=policy.no_speech_token)
             return eng.generate(None, prefix, max_length, suppress_tokens=None,
                                 begin_suppress_tokens=[220, s.eos_token_id], temperature=float(temperature),
                                 sample_uniforms=uniforms, return_stats=True, no_speech_token=policy.no_speech_token,

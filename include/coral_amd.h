@@ -398,6 +398,15 @@ typedef struct CaAttnDesc {
    * from row r: beam search reorders its hypotheses by rewriting this table, the K|V rows stay where the beam slot
    * that produced them wrote them.  Entries at t >= klen[r] are not read.  NULL = off (every row reads its own). */
   const int32_t* key_slot;
+  /* Optional, forward only: int32 [B] on the device, a per-row FIRST key beside the key count klen.  Keys and values
+   * t < kstart[b] of clip b contribute nothing to any query of that clip (score -inf before the softmax, probability 0),
+   * whatever finite values those rows hold: the left padding of a batch of decoder prompts of different lengths
+   * ($TF/models/whisper/generation_whisper.py, _prepare_decoder_input_ids: decoder_attention_mask).  A query without
+   * an allowed key - a causal row i < kstart[b], or kstart[b] >= klen[b] - gets an output row of zeros; its lse is
+   * unspecified.  Two forms: the causal forward at head_dim <= 64 (the decoder prefill), and the single-query decode
+   * form (Tq = 1, klen set, head_dim <= 64, not causal).  With dropout, O8, row_off, split_ws, key_slot or head_dim > 64,
+   * and in ca_attn_bwd and ca_decode_attn_qproj, it is CA_ERR_ARG.  NULL = off (every row starts at key 0). */
+  const int32_t* kstart;
   int64_t ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;
   int64_t sqb, skb, svb, sob, sdob, sdqb, sdkb, sdvb;
   int32_t B, H, Tq, Tk, hd, Tqp, causal;

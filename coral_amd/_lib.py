@@ -161,6 +161,17 @@ class CaBeamDesc(C.Structure):
                                               "tr_score")])
 
 
+class CaNgramTables(C.Structure):
+    """Mirror of `CaNgramTables` in include/coral_amd.h."""
+
+    ARRAYS = ("key", "ids", "count", "left", "adj", "ctx_slot", "suf_slot", "cstat", "prob", "keep", "ext")
+    _fields_ = ([("order", C.c_int32), ("reserved", C.c_int32), ("cap", C.c_int64 * 5)]
+                + [(n, C.c_void_p * 5) for n in ARRAYS] + [("gstat", C.c_void_p), ("status", C.c_void_p)])
+
+
+NGT_MAX_ORDER, NGT_MAX_WORD_BYTES, NGT_TOK_SPAN = 5, 255, 4096  # CA_NGT_*
+(NGT_ST_OVERFLOW, NGT_ST_LONG, NGT_ST_LONG_AT, NGT_ST_COLLISION, NGT_ST_PENDING, NGT_ST_MISS, NGT_ST_WORDS, NGT_ST_LINES,
+ NGT_ST_WORDS_N) = range(9)  # CA_NGT_ST_*
 BEAM_MAX_BEAMS, BEAM_MAX_ROWS = 16, 128  # CA_BEAM_MAX_BEAMS, CA_BEAM_MAX_ROWS
 ALIGN_MAX_TOKENS, ALIGN_MAX_FRAMES, ALIGN_MAX_HEADS, ALIGN_MAX_HEAD_DIM, ALIGN_MAX_FILTER_WIDTH = 447, 1500, 32, 128, 31  # CA_ALIGN_*
 
@@ -326,6 +337,16 @@ SIGNATURES = {
     "ca_allreduce_bucket": (C.c_int, [_vp, _vp, _i64, _i32]),
     "ca_reduce_scatter_bucket": (C.c_int, [_vp, _vp, _i64, _i32]),
     "ca_allgather_bucket": (C.c_int, [_vp, _vp, _i64, _i32]),
+    "ca_ngt_tokenize_blocks": (_i64, [_i64]),
+    "ca_ngt_tokenize": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "ca_ngt_vocab_round": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "ca_ngt_vocab_commit": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "ca_ngt_count": (C.c_int, [C.POINTER(CaNgramTables), _vp, _vp, _vp, _i64, _i32, _vp]),
+    "ca_ngt_adjust": (C.c_int, [C.POINTER(CaNgramTables), _vp]),
+    "ca_ngt_stats": (C.c_int, [C.POINTER(CaNgramTables), _vp]),
+    "ca_ngt_probs": (C.c_int, [C.POINTER(CaNgramTables), _vp, _i64, _vp]),
+    "ca_ngt_prune": (C.c_int, [C.POINTER(CaNgramTables), C.POINTER(C.c_int32), _vp]),
+    "ca_ngt_export": (C.c_int, [C.POINTER(CaNgramTables), _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
 }
 
 _lib = None

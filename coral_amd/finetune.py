@@ -1,6 +1,7 @@
 """`finetune(config)` — mirror of R/src/coral/finetune.py:21-95 on the MI355X engine: build the
 processor, model, data stream, collator and trainer from the ModelSetup, `trainer.train(...)`, save the
-model in HF layout.  The loop itself lives in `coral_amd.coral_trainer.CoralTrainer`."""
+model in HF layout and, for a wav2vec2 model with `use_decoder` and a `decoder_corpus_path`, train and store its n-gram
+language model.  The loop itself lives in `coral_amd.coral_trainer.CoralTrainer`."""
 
 from __future__ import annotations
 
@@ -17,8 +18,10 @@ logger = logging.getLogger(__package__)
 
 def finetune(config, n_examples: int | None = None) -> dict:
     """Finetune a model on a dataset - the reference's function, statement for statement where the hot path is
-    concerned (R/src/coral/finetune.py:21-95); experiment tracking, n-gram training and hub upload are out of scope
-    (DESIGN.md §7).  Returns a dict for callers and tests (the reference returns None)."""
+    concerned (R/src/coral/finetune.py:21-95); experiment tracking and hub upload are out of scope.  The
+    n-gram language model of a wav2vec2 model (R/src/coral/finetune.py:86-87) is trained on the GPU from the text file
+    `decoder_corpus_path`; building that corpus from `decoder_datasets` is out of scope.  Returns a dict
+    for callers and tests (the reference returns None)."""
     from .coral_trainer import EarlyStoppingCallback
 
     is_main_process = os.getenv("RANK", "0") == "0"
@@ -53,6 +56,13 @@ def finetune(config, n_examples: int | None = None) -> dict:
                         ignore_data_skip=config.get("ignore_data_skip", False))
     if is_main_process:
         model.save_pretrained(config.model_dir)
+        if config.model.get("use_decoder", False):
+            if config.get("decoder_corpus_path"):
+                from .ngram_train import train_and_store_ngram_model
+
+                train_and_store_ngram_model(config, device=model.engine.device)
+            else:
+                logger.info("use_decoder is set but decoder_corpus_path is not: no n-gram language model is trained.")
     return dict(history=trainer.state["log_history"], model=model, processor=processor, trainer=trainer,
                 steps_done=out.global_step, state=trainer.state, train_output=out)
 

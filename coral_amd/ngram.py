@@ -3,7 +3,8 @@
 The reference trains a KenLM 3-gram after a finetune and stores it in `model_dir/language_model/`
 (R/src/coral/ngram.py:322-358) for pyctcdecode.  Here the ARPA text file is read in plain Python (KenLM's binary
 format needs KenLM and is refused with a message), scored on the host in float64 for tests, and flattened into sorted
-hash tables the kernel binary-searches.  Training an n-gram is out of scope.
+hash tables the kernel binary-searches.  The n-gram itself is trained on the GPU by coral_amd/ngram_train.py (modified
+Kneser-Ney).
 
 Device tables, per million entries: 16 MB per million n-grams (8-byte hash + fp32 log10 p + fp32 back-off) and 12 MB
 per million unigram prefixes (8-byte hash + int32 word id; a word of n characters has n prefixes).
@@ -25,6 +26,7 @@ MASK64 = (1 << 64) - 1
 PREFIX_SEED = 0x243F6A8885A308D3   # label-string prefixes (kernel side only; here for the tests)
 WORD_SEED = 0x13198A2E03707344     # open word, over symbol ids
 NGRAM_SEED = 0xA4093822299F31D0    # n-grams, over word ids
+TOKEN_SEED = 0x082EFA98EC4E6C89    # corpus words, over their UTF-8 bytes (the tokeniser of coral_amd/csrc/ngram_train.hip)
 
 # Decoder parameters and their defaults (recalled pyctcdecode defaults; nothing rests on them being that).
 DEFAULT_PARAMS = dict(alpha=0.5, beta=1.5, unk_score_offset=-10.0, score_boundary=True, token_min_logp=-5.0,

@@ -19,7 +19,7 @@ __all__ = ["KMAJOR", "MNMAJOR", "EPI_NONE", "EPI_GELU", "EPI_RESIDUAL", "EPI_DGE
            "EPI_GELU_RESIDUAL", "CoralAmdError"]
 
 _ELT = {torch.bfloat16: 2, torch.float32: 4, torch.int32: 4, torch.uint8: 1, torch.int64: 8, torch.int16: 2,
-        torch.uint32: 4}
+        torch.uint32: 4, torch.float64: 8}
 
 
 def _stream() -> int:
@@ -972,3 +972,66 @@ def attn_bwd(Q, K, V, O, lse, dO, Dq, dQ, dK, dV, *, lddo, sdob, lddq, lddk, ldd
     d.lddo, d.sdob = lddo, sdob
     d.lddq, d.lddk, d.lddv, d.sdqb, d.sdkb, d.sdvb = lddq, lddk, lddv, sdqb, sdkb, sdvb
     check(lib().ca_attn_bwd(C.byref(d), _stream()), "ca_attn_bwd")
+
+
+# ---- modified Kneser-Ney n-gram training (ca_ngt_*; coral_amd/ngram_train.py drives the stages) --------------------
+def ngt_tables_desc(order, arrays, gstat, status):
+    """CaNgramTables from `arrays[name][o]` (device tensors laid out as include/coral_amd.h states), gstat and status."""
+    d = _lib.CaNgramTables()
+    d.order = order
+    for name in _lib.CaNgramTables.ARRAYS:
+        for o in range(order):
+            getattr(d, name)[o] = _p(arrays[name][o])
+    for o in range(order):
+        d.cap[o] = arrays["key"][o].numel()
+    d.gstat, d.status = _p(gstat), _p(status)
+    return d
+
+
+def ngt_tokenize_blocks(n):
+    return lib().ca_ngt_tokenize_blocks(n)
+
+
+def ngt_tokenize(text, n, base_off, hash_bits, blk, w_start, w_len, w_line, w_hash, status):
+    check(lib().ca_ngt_tokenize(_p(text), n, base_off, hash_bits, _p(blk), _p(w_start), _p(w_len), _p(w_line), _p(w_hash),
+                                w_start.numel(), _p(status), _stream()), "ca_ngt_tokenize")
+
+
+def ngt_vocab_round(vkey, vrep, varena_at, text, n, base_off, arena, w_start, w_len, w_hash, w_skip, w_slot, w_cand, nw, status):
+    check(lib().ca_ngt_vocab_round(_p(vkey), _p(vrep), _p(varena_at), vkey.numel(), _p(text), n, base_off, _p(arena),
+                                   _p(w_start), _p(w_len), _p(w_hash), _p(w_skip), _p(w_slot), _p(w_cand), nw, _p(status),
+                                   _stream()), "ca_ngt_vocab_round")
+
+
+def ngt_vocab_commit(vkey, vrep, varena_at, text, base_off, arena, arena_top, w_start, w_len, w_slot, nw, new_slot, new_count,
+                     status):
+    check(lib().ca_ngt_vocab_commit(_p(vkey), _p(vrep), _p(varena_at), vkey.numel(), _p(text), base_off, _p(arena),
+                                    _p(arena_top), arena.numel(), _p(w_start), _p(w_len), _p(w_slot), nw, _p(new_slot),
+                                    _p(new_count), _p(status), _stream()), "ca_ngt_vocab_commit")
+
+
+def ngt_count(desc, w_slot, slot_id, w_line, nw, seed_unk):
+    check(lib().ca_ngt_count(C.byref(desc), _p(w_slot), _p(slot_id), _p(w_line), nw, int(bool(seed_unk)), _stream()),
+          "ca_ngt_count")
+
+
+def ngt_adjust(desc):
+    check(lib().ca_ngt_adjust(C.byref(desc), _stream()), "ca_ngt_adjust")
+
+
+def ngt_stats(desc):
+    check(lib().ca_ngt_stats(C.byref(desc), _stream()), "ca_ngt_stats")
+
+
+def ngt_probs(desc, disc, vocab):
+    check(lib().ca_ngt_probs(C.byref(desc), _p(disc), vocab, _stream()), "ca_ngt_probs")
+
+
+def ngt_prune(desc, tau):
+    arr = (C.c_int32 * len(tau))(*[int(x) for x in tau])
+    check(lib().ca_ngt_prune(C.byref(desc), arr, _stream()), "ca_ngt_prune")
+
+
+def ngt_export(desc, n, disc, out_ids, out_int, out_f, out_n):
+    check(lib().ca_ngt_export(C.byref(desc), n, _p(disc), _p(out_ids), _p(out_int), _p(out_f), out_f.shape[0], _p(out_n),
+                              _stream()), "ca_ngt_export")

@@ -954,6 +954,100 @@ int ca_allreduce_bucket(CaComm* ctx, void* buf, int64_t n, int32_t dtype);
 int ca_reduce_scatter_bucket(CaComm* ctx, void* buf, int64_t n_per_rank, int32_t dtype);
 int ca_allgather_bucket(CaComm* ctx, void* buf, int64_t n_per_rank, int32_t dtype);
 
+/* ------------------------------------------------------------------------------------
+ * Modified Kneser-Ney n-gram training (coral_amd/ngram_train.py::train_ngram; the estimator: DESIGN.md §8; the stages
+ * and the table protocol: header comment of coral_amd/csrc/ngram_train.hip).  The corpus is fed in chunks of raw bytes
+ * that end at a line end; the tables persist between the chunks.  Word ids: <unk> 0, <s> 1, </s> 2, corpus words from 3.
+ * Every entry enqueues its launches on `stream` and returns; none allocates or synchronises.  All sums are integer
+ * atomics (bit-reproducible); every probe loop is bounded.
+ *
+ * status uint64 [CA_NGT_ST_WORDS_N] on the device, zero before the first call except CA_NGT_ST_LONG_AT = ~0:
+ *   CA_NGT_ST_OVERFLOW  bit 0: vocabulary table full; bit n (1..5): n-gram table of order n full; bit 6: word arena full;
+ *                       bit 7: more words than max_words; bit 8: more exported rows than out_cap.  A set bit means the
+ *                       results are incomplete and must be thrown away.
+ *   CA_NGT_ST_LONG / _LONG_AT  words above CA_NGT_MAX_WORD_BYTES bytes and the smallest corpus offset of one.
+ *   CA_NGT_ST_COLLISION two different id tuples with one 64-bit n-gram hash were seen (the run is refused).
+ *   CA_NGT_ST_PENDING   words of the last ca_ngt_vocab_round that differ from the word they were compared with.
+ *   CA_NGT_ST_MISS      an internal look-up failed (a word without id, a gram whose suffix was never counted).
+ *   CA_NGT_ST_WORDS / _LINES  words and line feeds of the last ca_ngt_tokenize.
+ *
+ * ca_ngt_tokenize: text uint8 [n], 1 <= n < 2^31.  Words are maximal runs of bytes other than space, tab, CR and LF.
+ *   For word i of the chunk, in order: w_start int32 = its byte offset in the chunk, w_len int32 (1..255), w_line int32 =
+ *   the number of line feeds in front of it in the chunk, w_hash uint64 = the rolling hash `mix64` of coral_amd/ngram.py
+ *   over its bytes under TOKEN_SEED, cut to its low hash_bits bits (64 in production; fewer only to test the compare on
+ *   probe) and never 0.  One workgroup handles CA_NGT_TOK_SPAN bytes; blk int32 [2 * ca_ngt_tokenize_blocks(n)] is
+ *   scratch.  base_off = the chunk's offset in the corpus (for CA_NGT_ST_LONG_AT).  Room for max_words words.
+ * ca_ngt_vocab_round / ca_ngt_vocab_commit: the vocabulary table of `cap` slots (a power of two): vkey uint64 (0 =
+ *   empty), vrep uint64 (smallest corpus offset << 8 | length of the word, ~0 before any), varena_at int64 (-1 before the
+ *   commit).  Per chunk: w_slot = -1, w_skip = 0, then rounds (status[CA_NGT_ST_PENDING] = 0 before each) until none is
+ *   pending: w_slot int32 [nw] = the word's slot; bytes are compared, so words that share a hash take different slots.
+ *   The commit copies every new word's bytes into arena uint8 [arena_cap] at varena_at (arena_top uint64 [1] = bytes
+ *   used) and lists the new slots in new_slot int32 [nw], new_count uint64 [1] (zero before the call), in no fixed order.
+ * ca_ngt_count: inserts every n-gram of orders 1..order of the chunk into the tables and adds to its raw count.
+ *   slot_id int32 [cap of the vocabulary] = word id of a slot.  seed_unk != 0 also inserts the unigram <unk>, count 0.
+ * ca_ngt_adjust (once, after the last chunk): suffix and prefix slots, distinct left extensions, adjusted counts.
+ * ca_ngt_stats (once): count-of-counts gstat[4 (n-1) + k-1] = t_{n,k}; gstat[20..23] = Z, N_1, N_2, N_3 of the empty
+ *   context; cstat[o][4 s ..] = Z, N_1, N_2, N_3 of the context in slot s of the table of order o + 1.
+ * ca_ngt_probs: prob[o] = p_{o+1} in fp64; disc double [20] on the device, disc[4 (n-1) + k] = D_n(k), D_n(0) = 0;
+ *   vocab = |W|, the three reserved words included.
+ * ca_ngt_prune: tau int32 [order] on the HOST, tau[0] = 0; ext zero before the call.  keep[o][s] = 1 for written grams.
+ * ca_ngt_export: the kept grams of order n, in no fixed order, out_n uint64 [1] (zero before) of them: out_ids int32
+ *   [out_cap, n]; out_int uint32 [out_cap, 6] = raw count, adjusted count, Z, N_1, N_2, N_3 of the gram as a context;
+ *   out_f double [out_cap, 2] = log10 p (0 for <s>) and log10 back-off (0 where the gram is no context).
+ * Table arrays, per order o + 1 with cap[o] slots (a power of two): key uint64 (zeros), ids uint64 [3 cap] (all ones),
+ *   count / left / adj uint32 (zeros), ctx_slot / suf_slot int32, cstat uint32 [4 cap] (zeros), prob double, keep / ext
+ *   uint8 (zeros); gstat uint64 [24] (zeros).
+ * ---------------------------------------------------------------------------------- */
+#define CA_NGT_MAX_ORDER 5
+#define CA_NGT_MAX_WORD_BYTES 255
+#define CA_NGT_TOK_SPAN 4096
+#define CA_NGT_ST_OVERFLOW 0
+#define CA_NGT_ST_LONG 1
+#define CA_NGT_ST_LONG_AT 2
+#define CA_NGT_ST_COLLISION 3
+#define CA_NGT_ST_PENDING 4
+#define CA_NGT_ST_MISS 5
+#define CA_NGT_ST_WORDS 6
+#define CA_NGT_ST_LINES 7
+#define CA_NGT_ST_WORDS_N 8
+typedef struct CaNgramTables {
+  int32_t order;
+  int32_t reserved;
+  int64_t cap[5];
+  uint64_t* key[5];
+  uint64_t* ids[5];
+  uint32_t* count[5];
+  uint32_t* left[5];
+  uint32_t* adj[5];
+  int32_t* ctx_slot[5];
+  int32_t* suf_slot[5];
+  uint32_t* cstat[5];
+  double* prob[5];
+  uint8_t* keep[5];
+  uint8_t* ext[5];
+  uint64_t* gstat;
+  uint64_t* status;
+} CaNgramTables;
+int64_t ca_ngt_tokenize_blocks(int64_t n);
+int ca_ngt_tokenize(const uint8_t* text, int64_t n, int64_t base_off, int32_t hash_bits, int32_t* blk, int32_t* w_start,
+                    int32_t* w_len, int32_t* w_line, uint64_t* w_hash, int64_t max_words, uint64_t* status, void* stream);
+int ca_ngt_vocab_round(uint64_t* vkey, uint64_t* vrep, int64_t* varena_at, int64_t cap, const uint8_t* text, int64_t n,
+                       int64_t base_off, const uint8_t* arena, const int32_t* w_start, const int32_t* w_len,
+                       const uint64_t* w_hash, int32_t* w_skip, int32_t* w_slot, int32_t* w_cand, int64_t nw,
+                       uint64_t* status, void* stream);
+int ca_ngt_vocab_commit(uint64_t* vkey, uint64_t* vrep, int64_t* varena_at, int64_t cap, const uint8_t* text,
+                        int64_t base_off, uint8_t* arena, uint64_t* arena_top, int64_t arena_cap, const int32_t* w_start,
+                        const int32_t* w_len, const int32_t* w_slot, int64_t nw, int32_t* new_slot, uint64_t* new_count,
+                        uint64_t* status, void* stream);
+int ca_ngt_count(const CaNgramTables* t, const int32_t* w_slot, const int32_t* slot_id, const int32_t* w_line, int64_t nw,
+                 int32_t seed_unk, void* stream);
+int ca_ngt_adjust(const CaNgramTables* t, void* stream);
+int ca_ngt_stats(const CaNgramTables* t, void* stream);
+int ca_ngt_probs(const CaNgramTables* t, const double* disc, int64_t vocab, void* stream);
+int ca_ngt_prune(const CaNgramTables* t, const int32_t* tau, void* stream);
+int ca_ngt_export(const CaNgramTables* t, int32_t n, const double* disc, int32_t* out_ids, uint32_t* out_int, double* out_f,
+                  int64_t out_cap, uint64_t* out_n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

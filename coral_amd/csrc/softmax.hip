@@ -59,13 +59,15 @@ __global__ __launch_bounds__(1024) void ce_kernel(const float* __restrict__ lg,
   if (threadIdx.x == 0) {
     float s = 0.f;
     for (int w = 0; w < 16; ++w) s += red[w];
-    const float lse = mx + __logf(s);
-    bc = lse;
-    atomicAdd(loss_sum, lse - l[lab]);
+    // everything stays relative to the row maximum: mx + log(s) rounds to an ulp of |mx|, which a row shifted by 1e4
+    // saw as 5e-4 relative on every gradient entry (log_softmax is shift-invariant, the sum mx + log(s) is not)
+    const float ls = __logf(s);
+    bc = ls;
+    atomicAdd(loss_sum, ls - (l[lab] - mx));
     atomicAdd(count, 1);
   }
   __syncthreads();
-  const float lse = bc;
+  const float ls = bc;
   if (g) {
     for (int c = threadIdx.x; c < n4; c += 1024) {
       const f32x4_t v = *(const f32x4_t*)(l + 4 * c);
@@ -73,7 +75,7 @@ __global__ __launch_bounds__(1024) void ce_kernel(const float* __restrict__ lg,
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int col = 4 * c + e;
-        o[e] = col < V ? __expf(v[e] - lse) - (col == lab ? 1.f : 0.f) : 0.f;
+        o[e] = col < V ? __expf((v[e] - mx) - ls) - (col == lab ? 1.f : 0.f) : 0.f;
       }
       *(f32x4_t*)(g + 4 * c) = o;
     }

@@ -748,10 +748,15 @@ def argmax_masked(logits, suppress, out, rows, V, ldv):
           "ca_argmax_masked")
 
 
+def _check_books(name, done, ids):
+    """The state every advancing pick moves: `done` as the kernel's bytes, `ids` with rows the kernel can index."""
+    if done.dtype != torch.bool or ids.dtype != torch.int64 or ids.dim() != 2 or ids.stride(1) != 1:
+        raise CoralAmdError(f"{name}: done must be bool, ids a row-major int64 matrix")
+
+
 def argmax_advance(logits, suppress, out, rows, V, ldv, done, ids, tok, pos, klen, pad_id, eos_id):
     """argmax_masked + the greedy step's bookkeeping (record the token, finished rows take pad, move the cursors)."""
-    if done.dtype != torch.bool or ids.dtype != torch.int64 or ids.dim() != 2 or ids.stride(1) != 1:
-        raise CoralAmdError("argmax_advance: done must be bool, ids a row-major int64 matrix")
+    _check_books("argmax_advance", done, ids)
     check(lib().ca_argmax_advance(_p(logits), _p(suppress), _p(out), rows, V, ldv, done.data_ptr(), _p(ids), ids.stride(0),
                                   _p(tok), _p(pos), _p(klen), int(pad_id), int(eos_id), _stream()), "ca_argmax_advance")
 
@@ -773,8 +778,7 @@ def argmax_timestamps(logits, suppress, out, rows, V, ldv, ids, pos, begin_index
 def argmax_timestamps_advance(logits, suppress, out, rows, V, ldv, done, ids, tok, pos, klen, pad_id, eos_id, begin_index,
                               timestamp_begin, max_initial_timestamp_index=None):
     """argmax_timestamps + the bookkeeping of argmax_advance (ids / pos are the history and the state it moves)."""
-    if done.dtype != torch.bool or ids.dtype != torch.int64 or ids.dim() != 2 or ids.stride(1) != 1:
-        raise CoralAmdError("argmax_timestamps_advance: done must be bool, ids a row-major int64 matrix")
+    _check_books("argmax_timestamps_advance", done, ids)
     check(lib().ca_argmax_timestamps_advance(_p(logits), _p(suppress), _p(out), rows, V, ldv, done.data_ptr(), _p(ids),
                                              ids.stride(0), _p(tok), _p(pos), _p(klen), int(pad_id), int(eos_id),
                                              int(begin_index), int(timestamp_begin), _cap(max_initial_timestamp_index),
@@ -787,8 +791,7 @@ def pick_scored_advance(logits, suppress, out, rows, V, ldv, inv_temperature, un
     inverse CDF on uniforms[r, pos[r] + 1]; the token's log-probability goes to sum_logprob / n_scored.
     timestamps: (begin_index, timestamp_begin, max_initial_timestamp_index) for Whisper's timestamp rules over the history
     in `ids`, None for the suppress mask alone."""
-    if done.dtype != torch.bool or ids.dtype != torch.int64 or ids.dim() != 2 or ids.stride(1) != 1:
-        raise CoralAmdError("pick_scored_advance: done must be bool, ids a row-major int64 matrix")
+    _check_books("pick_scored_advance", done, ids)
     if sum_logprob.dtype != torch.float32 or n_scored.dtype != torch.int32 or pos.dtype != torch.int32:
         raise CoralAmdError("pick_scored_advance: sum_logprob must be float32, n_scored and pos int32")
     ld_u = 0

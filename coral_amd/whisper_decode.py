@@ -410,7 +410,7 @@ class WhisperDecoding:
         finished rows), done |= eos, tok = the token, pos += 1, klen += 1."""
         B, V = g["tok"].numel(), self.s.vocab_size
         books = (g["done"], g["out"], g["tok"], g["pos"], g["klen"], g["pad_id"], g["eos"])
-        if g.get("scored") is not None:  # greedy or sampled, with the token's log-probability (csrc/sample.hip)
+        if g.get("scored") is not None:  # greedy or sampled, with the token's log-probability (csrc/pick.hip)
             sc = g["scored"]
             ops.pick_scored_advance(logits, suppress, g["nxt"], B, V, ldv, sc["inv_t"], sc["uniforms"], sc["sum_logprob"],
                                     sc["n_scored"], *books, timestamps=g.get("ts"))

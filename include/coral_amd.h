@@ -747,7 +747,8 @@ int ca_argmax_masked(const float* logits, const uint8_t* suppress, int32_t* out,
 /* The same argmax and, in the same launch, the bookkeeping of a greedy step
  * ($TF/generation/utils.py `_sample`: finished rows take pad, `unfinished_sequences` falls on eos): with t = done[r] ?
  * pad_id : out[r]:  ids[r, pos[r] + 1] = t;  done[r] |= t == eos_id;  tok[r] = t;  pos[r] += 1;  klen[r] += 1.  All state
- * lives in device memory, so the step replays as part of a graph. */
+ * lives in device memory, so the step replays as part of a graph.  A row whose pos[r] + 1 lies outside [0, ld_ids) stores
+ * no id; the rest of its bookkeeping still happens (the same holds for every *_advance pick below). */
 int ca_argmax_advance(const float* logits, const uint8_t* suppress, int32_t* out, int64_t rows, int32_t V, int64_t ldv,
                       uint8_t* done, int64_t* ids, int64_t ld_ids, int32_t* tok, int32_t* pos, int32_t* klen,
                       int32_t pad_id, int32_t eos_id, void* stream);
@@ -769,7 +770,7 @@ int ca_argmax_timestamps_advance(const float* logits, const uint8_t* suppress, i
                                  int64_t ldv, uint8_t* done, int64_t* ids, int64_t ld_ids, int32_t* tok, int32_t* pos,
                                  int32_t* klen, int32_t pad_id, int32_t eos_id, int32_t begin_index,
                                  int32_t timestamp_begin, int32_t max_initial_timestamp_index, void* stream);
-/* The scored pick of Whisper's temperature fallback (csrc/sample.hip; generate_with_fallback,
+/* The scored pick of Whisper's temperature fallback (csrc/pick.hip; generate_with_fallback,
  * $TF/models/whisper/generation_whisper.py): one launch per token with the bookkeeping of ca_argmax_advance, all state in
  * device memory.  The allowed set of a row: with `history` (normally `ids` itself, leading dimension ld_ids) what
  * ca_argmax_timestamps leaves - suppress mask, text and timestamp windows, and no text at all if

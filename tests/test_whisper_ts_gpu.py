@@ -181,6 +181,62 @@ def test_advance_variant_keeps_the_books_of_argmax_advance():
     assert want_tok[4] == pad and want_done.tolist() == [False, False, True, False, True]
 
 
+@pytest.mark.parametrize("entry", ["argmax_advance", "argmax_timestamps_advance", "pick_scored_advance"])
+def test_a_full_row_stores_no_id_and_still_keeps_its_books(entry):
+    """Rows 0 and 2 stand at the last column of `ids`: their token has no cell (pos + 1 == ld_ids) and must not be stored
+    - an unchecked store lands in the next row's first cell and, for the last row, behind the table, both of which lie
+    inside the flat buffer here -, while out, tok, pos, klen and done move as for row 1, which has one cell left."""
+    from coral_amd import ops
+
+    rows, V, ldv, L, begin = 3, 1565, 1568, 16, 4
+    tb, eos, pad, cap = R.TIMESTAMP_BEGIN, R.EOS, R.EOS, 50
+    g = torch.Generator().manual_seed(16)
+    hists = [[tb + 3] + [5 + i for i in range(L - begin - 1)],           # open segments, text last
+             [tb + 3, 7, tb + 40, tb + 40] + [9 + i for i in range(L - begin - 5)],
+             [tb + 1] + [3 + i for i in range(L - begin - 1)]]
+    assert [begin + len(h) - 1 for h in hists] == [L - 1, L - 2, L - 1]
+    flat = torch.full((rows * L + 8,), -5, dtype=torch.int64)
+    table, pos = _ids_table(g, hists, begin, L, tb)
+    flat[:rows * L] = table.flatten()
+    lg = _grid_logits(g, rows, V, ldv, 3e-3)
+    done = torch.tensor([False, False, True])  # row 2 had finished: it takes pad
+    klen, tok = (pos + 1).clone(), torch.zeros(rows, dtype=torch.int32)
+    picks = []
+    for r, h in enumerate(hists):
+        x = lg[r, :V].double().numpy()
+        if entry != "argmax_advance":
+            x, info = R.timestamp_rules(x, h, tb, eos, cap, detail=True)
+            assert abs(info["lse"] - info["text_max"]) >= 1e-3, "near-tie in the fixture"
+        picks.append(R.pick(x))
+    # the reference bookkeeping on a table one column wider: the column the full rows have not got takes their token
+    wide = np.concatenate([table.numpy(), np.full((rows, 1), -5, dtype=np.int64)], axis=1)
+    want_done, want_tok, want_pos, want_klen = done.numpy().copy(), tok.numpy().copy(), pos.numpy().copy(), klen.numpy().copy()
+    R.advance(wide, want_done, want_tok, want_pos, want_klen, picks, pad, eos)
+    want_flat = flat.numpy().copy()
+    want_flat[1 * L + L - 1] = picks[1]
+    assert np.array_equal(want_flat[:rows * L].reshape(rows, L), wide[:, :L])
+
+    flat_d = flat.to(DEV)
+    ids = flat_d[:rows * L].view(rows, L)
+    d = dict(done=done.to(DEV), tok=tok.to(DEV), pos=pos.to(DEV), klen=klen.to(DEV))
+    out = torch.full((rows,), -7, dtype=torch.int32, device=DEV)
+    head = (lg.to(DEV), None, out, rows, V, ldv)
+    books = (d["done"], ids, d["tok"], d["pos"], d["klen"], pad, eos)
+    if entry == "argmax_advance":
+        ops.argmax_advance(*head, *books)
+    elif entry == "argmax_timestamps_advance":
+        ops.argmax_timestamps_advance(*head, *books, begin, tb, cap)
+    else:
+        slp, ns = torch.zeros(rows, device=DEV), torch.zeros(rows, dtype=torch.int32, device=DEV)
+        ops.pick_scored_advance(*head, 0.0, None, slp, ns, *books, timestamps=(begin, tb, cap))
+    torch.cuda.synchronize()
+    assert out.tolist() == picks
+    assert np.array_equal(flat_d.cpu().numpy(), want_flat)
+    assert d["tok"].cpu().tolist() == want_tok.tolist() and d["pos"].cpu().tolist() == want_pos.tolist() == [L, L - 1, L]
+    assert d["klen"].cpu().tolist() == want_klen.tolist() and d["done"].cpu().tolist() == want_done.tolist()
+    assert want_tok[2] == pad and picks[1] != -5
+
+
 # ---- the engine ------------------------------------------------------------------------------------------------------------
 _STATE = {}
 

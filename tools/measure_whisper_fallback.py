@@ -7,7 +7,7 @@ time of `WhisperEngine.generate` to P + 3 + tokens minus the same call to P + 3,
 K|V are computed once in front and passed in, so no variant runs the encoder):
   (a) the greedy pick of generate(return_timestamps=True) as it was (ca_argmax_timestamps_advance);
   (b) the scored pick at temperature 0 (return_stats=True) and (c) at temperature 0.4 (ca_pick_scored_advance);
-  (d) the three pick launches alone at 16 x V;
+  (d) the four pick launches alone at 16 x V (ca_argmax_advance, ca_argmax_timestamps_advance, the scored pick twice);
   (e) one fallback attempt over 4 of the 16 clips: with a gather of the cross K|V against encoder + projection again.
 One JSON line at the end.
 
@@ -92,6 +92,11 @@ def main(argv=None):
     def reset():
         st["pos"].fill_(P + 1)
 
+    def plain():
+        reset()
+        ops.argmax_advance(logits, supm, st["out"], B, V, Vp, st["done"], st["ids"], st["tok"], st["pos"], st["klen"],
+                           shape.pad_token_id, shape.eos_token_id)
+
     def greedy():
         reset()
         ops.argmax_timestamps_advance(logits, supm, st["out"], B, V, Vp, st["done"], st["ids"], st["tok"], st["pos"], st["klen"],
@@ -106,7 +111,8 @@ def main(argv=None):
         return run
 
     fill = event_mean_ms(reset, 50)
-    res["argmax_timestamps_us"] = 1e3 * (event_mean_ms(greedy, 50) - fill)
+    res["argmax_advance_us"] = 1e3 * (event_mean_ms(plain, 50) - fill)
+    res["argmax_timestamps_us"] =1e3 * (event_mean_ms(greedy, 50) - fill)
     res["pick_scored_t0_us"] = 1e3 * (event_mean_ms(scored(0.0), 50) - fill)
     res["pick_scored_t04_us"] = 1e3 * (event_mean_ms(scored(2.5), 50) - fill)
 

@@ -184,6 +184,9 @@ def align_ws_bytes_per_clip(A, Lw, Fmax):
 FP8_GROUP_MAX = 8  # CA_FP8_GROUP_MAX
 CTC_COLLAPSE_TILE = 4096  # CA_CTC_COLLAPSE_TILE
 CTC_ALIGN_MAX_LABELS = 4095  # CA_CTC_ALIGN_MAX_LABELS
+EDIT_MAX_TOKENS = (1 << 20) - 1  # CA_EDIT_MAX_TOKENS
+EDIT_WAVE_MAX = 1024  # CA_EDIT_WAVE_MAX
+EDIT_PANEL = 2048  # CA_EDIT_PANEL
 KMAJOR, MNMAJOR = 0, 1
 EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_DGELU, EPI_GELU_RESIDUAL = 0, 1, 2, 3, 4
 
@@ -271,6 +274,8 @@ SIGNATURES = {
     "ca_ctc_align_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "ca_ctc_align": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32,
                                _vp]),
+    "ca_edit_counts_workspace_bytes": (_i64, [_i32, _i64, _i64]),
+    "ca_edit_counts": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i64, _vp]),
     "ca_beam_select_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "ca_beam_select": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ca_beam_advance": (C.c_int, [C.POINTER(CaBeamDesc), _vp]),

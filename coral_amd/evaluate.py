@@ -2,8 +2,10 @@
 Whisper, by the saved architecture), transcribe the evaluation examples in batches (greedy CTC - or the LM-fused CTC
 beam search when the model directory holds `language_model/*.arpa` and `no_lm` is false -, or log-mel +
 greedy `generate(language="danish", task="transcribe")`, on the GPU), normalise both sides like the reference
-(lower / strip) and report CER / WER.  The demographic slicing of the
-reference (`get_score_df`, :161-216) is pandas reporting and out of scope."""
+(lower / strip) and report CER / WER.  `error_rates: device` takes the rates from alignment counts computed on the
+GPU (coral_amd/error_rates.py) and opens the reference's normalised rates (`normalise_error_rates`) and its demographic
+slicing (`get_score_df`, :161-216, restated without pandas: `score_categories`); the default, `host`, is
+coral_amd/metrics.py as before."""
 
 from __future__ import annotations
 
@@ -275,6 +277,15 @@ def evaluate(config, examples: list | None = None) -> dict:
     pipeline-based `evaluate` (R/src/coral/evaluate.py:29-85, :123-158)."""
     from .config import DictConfig
 
+    from .error_rates import batch_scores, check_options, score_table
+
+    categories = list(config.get("score_categories", None) or [])
+    normalise = bool(config.get("normalise_error_rates", False) or False)
+    on_device = check_options(config.get("error_rates", "host"), normalise, categories)
+    for i, e in enumerate(examples or []):  # before anything is transcribed
+        for c in categories:
+            if c not in e:
+                raise ValueError(f"score_categories: example {i} has no {c!r}")
     model_dir = config.get("model_dir", config.model_id)
     mtype = saved_model_type(model_dir)
     chunk_length_s = config.get("chunk_length_s", 0) or 0
@@ -324,10 +335,23 @@ def evaluate(config, examples: list | None = None) -> dict:
     preds = [p.lower().strip() for p in preds]
     labels = [e["text"].lower().strip() if config.lower_case else e["text"].strip() for e in examples]
     scores = dict(model_type=mtype, n=len(examples))
-    if any(labels):  # CER / WER need reference texts (a synthetic Whisper set has none: ids-only output)
+    table = None
+    if any(labels) and on_device:  # the same two rates from alignment counts (ca_edit_counts), and what only counts give
+        res = batch_scores(preds, labels, normalise, model.engine.device if hasattr(model, "engine") else "cuda")
+        scores.update(cer=res["cer"], wer=res["wer"],
+                      error_counts=dict(char=res["char_counts"].sum(0).tolist(), word=res["word_counts"].sum(0).tolist()))
+        if categories:
+            table = scores["score_table"] = score_table(examples, categories, res["char_counts"], res["word_counts"], normalise)
+    elif any(labels):  # CER / WER need reference texts (a synthetic Whisper set has none: ids-only output)
         scores.update(cer=cer(preds, labels), wer=wer(preds, labels))
+    name = str(config.model_id).replace("/", "--") + "." + str(config.dataset).split("::")[0].replace("/", "--")
+    if config.store_results and table is not None:
+        with Path(f"{name}.scores.csv").open("w", newline="") as f:
+            w = csv.DictWriter(f, fieldnames=categories + ["cer", "wer"])
+            w.writeheader()
+            w.writerows(table)
+        scores["scores_csv"] = f"{name}.scores.csv"
     if config.store_results:
-        name = str(config.model_id).replace("/", "--") + "." + str(config.dataset).split("::")[0].replace("/", "--")
         path = Path(f"{name}.csv")
         with path.open("w", newline="") as f:
             w = csv.writer(f)

@@ -165,11 +165,12 @@ def evaluate_split(model, examples, collator, compute_metrics, batch_size, rank=
     # ids are already collapsed: decode without grouping so genuine double letters survive
     tok = compute_metrics.keywords["processor"].tokenizer if hasattr(compute_metrics, "keywords") else None
     if tok is not None:
-        from .metrics import cer, wer
+        from .error_rates import text_rates
 
         ps = [tok.decode(r, group_tokens=False).lower().strip() for r in P]
         Lb2 = Lb.copy()
         Lb2[Lb2 == -100] = tok.pad_token_id
         ls = [tok.decode(r, group_tokens=False).lower().strip() for r in Lb2]
-        return dict(cer=cer(ps, ls), wer=wer(ps, ls))
+        kw = compute_metrics.keywords
+        return text_rates(ps, ls, kw.get("error_rates", "host"), kw.get("normalise_error_rates", False))
     return compute_metrics(P, Lb)

@@ -189,7 +189,9 @@ class Wav2Vec2ModelSetup(ModelSetup):
         return CoralTrainer
 
     def load_compute_metrics(self):
-        return partial(compute_error_rate_metrics, processor=self.processor)
+        return partial(compute_error_rate_metrics, processor=self.processor,
+                       error_rates=self.config.get("error_rates", "host") or "host",
+                       normalise_error_rates=bool(self.config.get("normalise_error_rates", False) or False))
 
     def load_training_arguments(self) -> TrainingArgs:
         return _training_args(self.config, self.config.model.learning_rate)

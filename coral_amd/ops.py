@@ -605,6 +605,76 @@ def ctc_align(logits, in_len, labels, lab_len, start, end, tok_score, score, ws,
           "ca_ctc_align")
 
 
+def edit_counts_workspace_bytes(n_pairs, max_ref_len, max_hyp_len):
+    return lib().ca_edit_counts_workspace_bytes(n_pairs, max_ref_len, max_hyp_len)
+
+
+def edit_counts_plan(ref, ref_off, hyp, hyp_off, device="cuda", route=0, order=None):
+    """Check one ragged batch of token strings on the host and upload it, in one copy, for `edit_counts_launch`.
+    ref / hyp: int32 tokens >= 0 laid end to end; ref_off / hyp_off: int64 [n + 1], starting at 0, non-decreasing and
+    ending at the token count; all host arrays (their values are checked here, where they start, as ctc_align checks its
+    labels).  order: the launch order, a permutation of range(n); None = by cell count, largest first.  route: 0 by
+    length, 1 the wave route (every side at most CA_EDIT_WAVE_MAX), 2 the workgroup route.  A pair the call could not
+    serve is refused here with CA_ERR_ARG: the library itself cannot see the lengths."""
+    import numpy as np
+
+    ref, hyp = np.ascontiguousarray(ref, dtype=np.int32).reshape(-1), np.ascontiguousarray(hyp, dtype=np.int32).reshape(-1)
+    ref_off = np.ascontiguousarray(ref_off, dtype=np.int64).reshape(-1)
+    hyp_off = np.ascontiguousarray(hyp_off, dtype=np.int64).reshape(-1)
+    n = len(ref_off) - 1
+    if n < 1 or len(hyp_off) != n + 1:
+        raise ValueError(f"edit_counts: ref_off and hyp_off must both hold n + 1 >= 2 offsets, got {len(ref_off)} and {len(hyp_off)}")
+    for name, off, toks in (("ref", ref_off, ref), ("hyp", hyp_off, hyp)):
+        if off[0] != 0 or off[-1] != len(toks) or bool((np.diff(off) < 0).any()):
+            raise ValueError(f"edit_counts: {name}_off must start at 0, not decrease and end at the {len(toks)} tokens of {name}")
+        if len(toks) and int(toks.min()) < 0:
+            raise ValueError(f"edit_counts: {name} tokens must be >= 0")
+    rl, hl = np.diff(ref_off), np.diff(hyp_off)
+    longest = np.maximum(rl, hl)
+    if int(longest.max()) > _lib.EDIT_MAX_TOKENS:
+        raise ValueError(f"edit_counts: pair {int(longest.argmax())} has a side of {int(longest.max())} tokens, the limit is "
+                         f"{_lib.EDIT_MAX_TOKENS} (CA_EDIT_MAX_TOKENS)")
+    if route not in (0, 1, 2):
+        raise CoralAmdError(f"ca_edit_counts failed (-1, CA_ERR_ARG): route {route} is not 0 (by length), 1 (wave) or 2 (workgroup)")
+    if route == 1 and int(longest.max()) > _lib.EDIT_WAVE_MAX:
+        raise CoralAmdError(f"ca_edit_counts failed (-1, CA_ERR_ARG): route 1 (wave) with pair {int(longest.argmax())} of "
+                            f"{int(longest.max())} tokens a side, above CA_EDIT_WAVE_MAX = {_lib.EDIT_WAVE_MAX}")
+    if order is None:  # by cell count, largest first (stable: equal pairs keep their order)
+        order = np.argsort(-(rl * hl), kind="stable")
+    order = np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
+    if len(order) != n or not np.array_equal(np.sort(order), np.arange(n, dtype=np.int32)):
+        raise ValueError("edit_counts: order must be a permutation of range(n_pairs)")
+    # the pairs that take the workgroup route, and their boundary columns
+    swept = (rl > 0) & (hl > 0) & ((longest > _lib.EDIT_WAVE_MAX) if route == 0 else np.full(n, route == 2))
+    ws_bytes = int((2 * (rl[swept] + 1) * 8).sum())
+    # one buffer, one copy: offsets (int64) first, then the int32 arrays (a token pointer stays valid when a side is empty)
+    parts = [ref_off, hyp_off, ref, hyp, order, np.zeros(2, dtype=np.int32)]
+    at, pos = [], 0
+    for a in parts:
+        at.append(pos)
+        pos += a.nbytes
+    host = torch.from_numpy(np.concatenate([a.view(np.uint8) for a in parts]))
+    dev = host.to(device)
+    return dict(buf=dev, at=at, n=n, route=int(route), ws=torch.empty(max(8, ws_bytes), dtype=torch.uint8, device=dev.device),
+                ws_bytes=ws_bytes, counts=torch.empty(n, 4, dtype=torch.int32, device=dev.device))
+
+
+def edit_counts_launch(plan):
+    """Enqueue ca_edit_counts on an uploaded batch.  -> counts int32 [n, 4] on the device (hits, substitutions, deletions,
+    insertions), the plan's own buffer: a second launch overwrites it."""
+    base, at = _p(plan["buf"]), plan["at"]
+    check(lib().ca_edit_counts(base + at[2], base + at[0], base + at[3], base + at[1], base + at[4], plan["n"],
+                               _p(plan["counts"]), plan["route"], _p(plan["ws"]), plan["ws_bytes"], _stream()),
+          "ca_edit_counts")
+    return plan["counts"]
+
+
+def edit_counts(ref, ref_off, hyp, hyp_off, device="cuda", route=0, order=None):
+    """Alignment counts of a ragged batch (ca_edit_counts): host arrays in (see `edit_counts_plan`), counts int32 [n, 4] =
+    hits, substitutions, deletions, insertions on the device out."""
+    return edit_counts_launch(edit_counts_plan(ref, ref_off, hyp, hyp_off, device, route, order))
+
+
 def mask_frames(h, tmask, fmask, embed, flen, B, T, Cn):
     check(lib().ca_mask_frames(_p(h), _p(tmask), _p(fmask), _p(embed), _p(flen), B, T, Cn,
                                _stream()), "ca_mask_frames")

@@ -461,7 +461,7 @@ class WhisperModelSetup(ModelSetup):
 
     def load_compute_metrics(self):
         def compute(pred_ids, label_ids):
-            from .metrics import cer, wer
+            from .error_rates import text_rates
 
             labels = np.array(label_ids, copy=True)
             labels[labels == -100] = self.model.shape.pad_token_id
@@ -469,7 +469,8 @@ class WhisperModelSetup(ModelSetup):
             labs = self.processor.batch_decode(labels, skip_special_tokens=True)
             preds = [p.lower().strip() for p in preds]
             labs = [x.lower().strip() for x in labs]
-            return dict(cer=cer(preds, labs), wer=wer(preds, labs))
+            return text_rates(preds, labs, self.config.get("error_rates", "host") or "host",
+                              bool(self.config.get("normalise_error_rates", False) or False))
 
         return compute
 

@@ -627,6 +627,41 @@ int ca_ctc_align(const float* logits, int64_t ldv, const int32_t* in_len, const 
                  int64_t ws_bytes, int32_t B, int32_t T, int32_t V, int32_t Lmax, int32_t blank, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Alignment counts for error rates (coral_amd/error_rates.py; csrc/edit.hip): for every pair (reference tokens r[0..n),
+ * hypothesis tokens h[0..m)) the hits, substitutions, deletions and insertions of a minimum-edit-distance alignment.
+ *   Tie rule: among the minimum-distance alignments, the one with the fewest insertions (equivalently the fewest
+ *   deletions and the most substitutions, I - D = m - n being fixed).  Computed without back-pointers as the shortest
+ *   path under the lexicographic order on (distance, insertions):  C[0][j] = (j, j), C[i][0] = (i, 0),
+ *   C[i][j] = lexmin(C[i-1][j-1] + (r != h, 0), C[i-1][j] + (1, 0), C[i][j-1] + (1, 1));  (d, I) = C[n][m],
+ *   D = I - (m - n), S = d - I - D, H = n - S - D.  n = 0 gives (0, 0, 0, m), m = 0 gives (0, 0, n, 0).
+ *   ref / hyp: int32 tokens >= 0 laid end to end (never NULL, also when every string is empty); ref_off / hyp_off int64
+ *   [n_pairs + 1], non-decreasing, pair p owning [off[p], off[p+1]), each side at most CA_EDIT_MAX_TOKENS long (the
+ *   caller checks values, offsets and `order`: coral_amd/ops.py does, on the host); order int32 [n_pairs]: the launch
+ *   order, a permutation of the pairs (largest first keeps one long pair from trailing the batch), NULL = identity;
+ *   counts int32 [n_pairs, 4] = hits, substitutions, deletions, insertions, in the pairs' own order.
+ *   route 0: by length - a pair with both sides <= CA_EDIT_WAVE_MAX is swept by one wavefront, any other by a whole
+ *   workgroup in panels of CA_EDIT_PANEL hypothesis columns; 1: the wave route for every pair; 2: the workgroup route
+ *   for every pair.  All pairs run in one launch.
+ *   ws: 8-byte aligned; only the workgroup route uses it: 16 (n + 1) bytes for every pair that takes it (two boundary
+ *   columns between panels), laid out in launch order by the kernel.  ca_edit_counts_workspace_bytes(n_pairs, longest
+ *   reference, longest hypothesis) is the bound n_pairs * 16 * (longest reference + 1); a caller that knows the lengths
+ *   may ask for the pairs of the workgroup route alone, and a batch that stays on the wave route may pass NULL / 0.
+ *   The lengths live on the device, so the call cannot refuse a pair by its length: a pair that cannot be served - route
+ *   1 with a side above CA_EDIT_WAVE_MAX, a side above CA_EDIT_MAX_TOKENS or a negative length, a workspace too small
+ *   for its reference - gets -1 in all four counts and touches no memory; a caller that knows the lengths refuses
+ *   before the launch (coral_amd/ops.py raises with CA_ERR_ARG).
+ *   Exact integers, no atomics: bit-identical from run to run and independent of `order`.  No allocation, no
+ *   synchronisation; bad arguments return CA_ERR_ARG with the function's name in ca_last_error().
+ * ---------------------------------------------------------------------------------- */
+#define CA_EDIT_MAX_TOKENS ((1 << 20) - 1)
+#define CA_EDIT_WAVE_MAX 1024
+#define CA_EDIT_PANEL 2048
+int64_t ca_edit_counts_workspace_bytes(int32_t n_pairs, int64_t max_ref_len, int64_t max_hyp_len);
+int ca_edit_counts(const int32_t* ref, const int64_t* ref_off, const int32_t* hyp, const int64_t* hyp_off,
+                   const int32_t* order, int32_t n_pairs, int32_t* counts, int32_t route, void* ws, int64_t ws_bytes,
+                   void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Small elementwise pieces of the wav2vec2 encoder.
  * ca_mask_frames: SpecAugment + padding ($TF/.../modeling_wav2vec2.py:1272-1316, 752-755):
  *   h[b,t,:] = embed where tmask[b,t]; h[b,t,c] = 0 where fmask[b,c]; h[b,t,:] = 0 for

@@ -187,6 +187,8 @@ CTC_ALIGN_MAX_LABELS = 4095  # CA_CTC_ALIGN_MAX_LABELS
 EDIT_MAX_TOKENS = (1 << 20) - 1  # CA_EDIT_MAX_TOKENS
 EDIT_WAVE_MAX = 1024  # CA_EDIT_WAVE_MAX
 EDIT_PANEL = 2048  # CA_EDIT_PANEL
+RESAMPLE_CHUNK, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_TABLE = 1024, 4096, 1 << 20  # CA_RESAMPLE_*
+RESAMPLE_LDS_BYTES = 163840  # CA_RESAMPLE_LDS_BYTES
 KMAJOR, MNMAJOR = 0, 1
 EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_DGELU, EPI_GELU_RESIDUAL = 0, 1, 2, 3, 4
 
@@ -247,6 +249,7 @@ SIGNATURES = {
     "ca_mix_noise": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _vp]),
     "ca_white_noise": (C.c_int, [_vp, _i64, C.c_uint64, _vp]),
     "ca_pcm_prepare": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _vp]),
+    "ca_resample": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _i32, _vp]),
     "ca_conv0_ln_gelu_fwd": (
         C.c_int,
         [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _f32, _vp],

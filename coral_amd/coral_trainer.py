@@ -17,7 +17,9 @@ holds before `process_example`, R/src/coral/data.py:704-757) take the device inp
 (SURVEY.md §8f rows N1 + N4): the host only packs PCM into pinned staging memory; peak normalisation,
 the augmentation chain (training only, as `augment_audio=True` there), zero-mean/unit-variance +
 padding + attention mask, or Whisper's pad/trim + log-mel, all run on the GPU, one batch ahead of the
-step that consumes them.  Examples that were featurised on the host (`input_values` /
+step that consumes them.  With `max_source_sampling_rate` in the training arguments, examples whose
+`audio["sampling_rate"]` is not the model's are resampled there first (coral_amd/resample.py); without it such an
+example raises.  Examples that were featurised on the host (`input_values` /
 `input_features`) go through the collator as in the reference.
 """
 
@@ -177,15 +179,16 @@ class CoralTrainer:
         # the reference's augmentation chain itself starts with PeakNormalization(p=1) (R/src/coral/data.py:709-711):
         # augmented training audio is peak-normalised also when normalise_audio is off
         peak = bool(getattr(a, "normalise_audio", True)) or aug is not None
+        rates = dict(max_source_rate=getattr(a, "max_source_sampling_rate", None), target_rate=sr)
         if self.is_seq2seq:
             from .whisper import N_SAMPLES
 
             return DeviceInputPipeline(self.engine.device, B, N_SAMPLES, kind="whisper", dtype=np.float32,
-                                       peak_normalize=peak, mel_filters=self.engine.mel_filters, augment=aug)
+                                       peak_normalize=peak, mel_filters=self.engine.mel_filters, augment=aug, **rates)
         n_max = int(sr * float(getattr(a, "max_seconds_per_example", 10.0)))
         return DeviceInputPipeline(self.engine.device, B, n_max, kind="wav2vec2", dtype=np.float32,
                                    padding=getattr(a, "padding", "longest") or "longest",
-                                   peak_normalize=peak, augment=aug)
+                                   peak_normalize=peak, augment=aug, **rates)
 
     def _pull(self, B: int):
         """B examples of the training stream, or None when the pass ran dry on some rank (`dataloader_drop_last`)."""
@@ -216,7 +219,9 @@ class CoralTrainer:
         if "audio" in feats[0] and getattr(self.args, "device_input_pipeline", True):
             if self._pipe is None:
                 self._pipe = self._build_pipeline(B)
-            self._pipe.submit([np.asarray(f["audio"]["array"]) for f in feats])
+            # (an example without a rate is at the model's; another rate needs `max_source_sampling_rate`)
+            self._pipe.submit([np.asarray(f["audio"]["array"]) for f in feats],
+                              sampling_rate=[f["audio"].get("sampling_rate") for f in feats])
             return ("raw", self._labels_of(feats))
         return ("host", self.data_collator(feats))
 

@@ -62,13 +62,16 @@ def chunks_of(ids, start, end, tok_score, tokenizer, level: str, align_to: int, 
 
 
 def align(model, processor, arrays: list, texts: list, batch_size: int = 16, chunk_length_s: float = 0,
-          stride_length_s=None, level: str = "word") -> list:
+          stride_length_s=None, level: str = "word", sampling_rate=None) -> list:
     """Forced alignment of texts[i] to arrays[i] -> per recording {"text", "score", "chunks": [{"text", "timestamp":
     (start_s, end_s), "score"}]}, one chunk per word (level="word") or per character ("char", the word delimiter as " ").
     "score" is the log-probability of the alignment, a chunk's the mean log-probability of its characters' frames.
     chunk_length_s > 0 runs the recordings in overlapping chunks as `transcribe` does and aligns to the stitched logits.
     A recording whose text cannot be aligned (more tokens, counting a gap between equal neighbours, than frames) gets
-    score = -inf and chunks = None; a text of more than CA_CTC_ALIGN_MAX_LABELS tokens raises."""
+    score = -inf and chunks = None; a text of more than CA_CTC_ALIGN_MAX_LABELS tokens raises.
+    sampling_rate: the rate of `arrays`, one int or one per recording (None: the extractor's); recordings at another rate
+    are resampled on the GPU first (coral_amd/resample.py)."""
+    from .resample import to_rate
     from .wav2vec2 import Wav2Vec2CTCEngine
 
     eng = getattr(model, "engine", None)
@@ -85,6 +88,8 @@ def align(model, processor, arrays: list, texts: list, batch_size: int = 16, chu
     if not arrays:
         return []
     sr = processor.feature_extractor.sampling_rate
+    if sampling_rate is not None:
+        arrays = to_rate(arrays, sampling_rate, sr, eng.device)
     align_to = int(math.prod(eng.s.conv_stride))
     model.eval()
     rows, scores = [], []

@@ -122,14 +122,22 @@ def load_data_for_finetuning(config, processor, n_examples: int | None = None, m
 def _npz_examples(root: Path, processor, text_column: str, sampling_rate: int, rank: int = 0, world: int = 1,
                   raw: bool = False):
     """Local shards, dealt round-robin to the ranks (file i goes to rank i % world) so that no two ranks train on the
-    same example — what `split_dataset_by_node` does for the reference's streaming datasets under accelerate."""
+    same example — what `split_dataset_by_node` does for the reference's streaming datasets under accelerate.
+    A shard with a `sampling_rate` entry keeps it (the raw path resamples in the device input pipeline, the host path
+    through coral_amd.resample here); a shard without one is at the model's rate."""
     for f in sorted(root.glob("*.npz"))[rank::world]:
         z = np.load(f, allow_pickle=True)
+        rate = int(z["sampling_rate"]) if "sampling_rate" in z.files else sampling_rate
         if raw:
-            ex = dict(audio=dict(array=z["audio"].astype(np.float32), sampling_rate=sampling_rate),
+            ex = dict(audio=dict(array=z["audio"].astype(np.float32), sampling_rate=rate),
                       input_length=len(z["audio"]))
         else:
-            ex = processor(z["audio"].astype(np.float32), sampling_rate=sampling_rate)
+            audio = z["audio"].astype(np.float32)
+            if rate != sampling_rate:
+                from .resample import resample
+
+                audio = resample([audio], rate, target=sampling_rate)[0]
+            ex = processor(audio, sampling_rate=sampling_rate)
             ex["input_length"] = len(ex["input_values"])
         ex["labels"] = processor(text=str(z[text_column]), truncation=True)["input_ids"]
         yield ex

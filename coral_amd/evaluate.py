@@ -25,7 +25,7 @@ logger = logging.getLogger(__package__)
 
 
 def transcribe(model, processor, arrays: list, batch_size: int = 16, chunk_length_s: float = 0, stride_length_s=None,
-               return_timestamps=None, timestamp_source: str = "emission"):
+               return_timestamps=None, timestamp_source: str = "emission", sampling_rate=None):
     """ASR-pipeline equivalent ($TF/pipelines/automatic_speech_recognition.py:345,569-575,679):
     feature-extract, forward, argmax over all frames, CTC collapse, decode.  -> list of texts.
     chunk_length_s > 0: overlapping chunks with the pipeline's `chunk_length_s` / `stride_length_s` semantics
@@ -33,13 +33,18 @@ def transcribe(model, processor, arrays: list, batch_size: int = 16, chunk_lengt
     [{"text", "timestamp": (start_s, stop_s)}]} instead (greedy decoding only, unless timestamp_source="alignment").
     A whole clip of more than 4096 frames (81.9 s), or one decoded with timestamps, is collapsed by
     `ca_ctc_collapse_offsets`.  timestamp_source="alignment": the times come from the CTC forced alignment of the decoded
-    ids to the same logits (`ca_ctc_align`) - with the greedy decoder and with the LM-fused beam search alike."""
+    ids to the same logits (`ca_ctc_align`) - with the greedy decoder and with the LM-fused beam search alike.
+    sampling_rate: the rate of `arrays`, one int or one per recording (None: the extractor's).  Recordings at another
+    rate are resampled on the GPU first (coral_amd/resample.py), so chunking and times see audio at the model's rate."""
     from .longform import align_rows, check_timestamp_mode, collapse_rows, decode_rows, transcribe_long
+    from .resample import to_rate
 
     with_lm = getattr(processor, "lm", None) is not None
     check_timestamp_mode(return_timestamps, with_lm, timestamp_source)
     if chunk_length_s is not None and chunk_length_s < 0:
         raise ValueError(f"chunk_length_s must be 0 (whole clips) or positive, got {chunk_length_s}")
+    if sampling_rate is not None:
+        arrays = to_rate(arrays, sampling_rate, processor.feature_extractor.sampling_rate, model.engine.device)
     if chunk_length_s:
         res = transcribe_long(model, processor, arrays, chunk_length_s, stride_length_s, batch_size, return_timestamps,
                               timestamp_source)
@@ -82,7 +87,8 @@ def transcribe(model, processor, arrays: list, batch_size: int = 16, chunk_lengt
 def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max_length: int | None = None,
                        num_beams: int = 1, return_timestamps: bool = False, temperature=None, logprob_threshold=None,
                        compression_ratio_threshold=None, no_speech_threshold=None, sample_seed: int = 0, prompt_ids=None,
-                       condition_on_prev_tokens=None, prompt_condition_type=None, prompt: str | None = None):
+                       condition_on_prev_tokens=None, prompt_condition_type=None, prompt: str | None = None,
+                       sampling_rate=None):
     """The Whisper branch of the ASR pipeline ($TF/pipelines/automatic_speech_recognition.py:345,529,600): pad / trim
     every clip to 30 s, log-mel on the GPU, `model.generate(input_features, language="danish", task="transcribe")`
     (R/src/coral/evaluate.py:56-60), decode the generated ids without special tokens.
@@ -105,7 +111,11 @@ def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max
     (coral_amd/longform_whisper.py `PromptPolicy`): every clip then takes the window loop, and a window's decoder input
     starts with the clip's text so far and / or the prompt, left-padded over the round's windows.  prompt: a string in
     place of prompt_ids, through the processor's (or its tokenizer's) `get_prompt_ids`.  With the fallback arguments a
-    window accepted at a temperature of 0.5 or more leaves the next one unconditioned.  Not with beams, not with "word"."""
+    window accepted at a temperature of 0.5 or more leaves the next one unconditioned.  Not with beams, not with "word".
+    sampling_rate: the rate of `arrays`, one int or one per recording (None: the extractor's).  Recordings at another
+    rate are resampled on the GPU first (coral_amd/resample.py); the 30 s rule then applies to the resampled audio."""
+    from .resample import to_rate
+
     model.eval()
     if prompt is not None:
         getter = getattr(processor, "get_prompt_ids", None) or getattr(getattr(processor, "tokenizer", None), "get_prompt_ids", None)
@@ -140,6 +150,8 @@ def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max
                              "implemented with beam search")
         if word:
             raise ValueError("return_timestamps=\"word\" is not implemented with prompt_ids / condition_on_prev_tokens")
+    if sampling_rate is not None:
+        arrays = to_rate(arrays, sampling_rate, processor.feature_extractor.sampling_rate, model.engine.device)
     looped = [i for i, a in enumerate(arrays)
               if return_timestamps or policy is not None or prompting is not None or len(a) > N_SAMPLES]
     if looped and num_beams > 1:
@@ -272,8 +284,9 @@ def saved_model_type(model_dir) -> str:
 
 
 def evaluate(config, examples: list | None = None) -> dict:
-    """config: evaluation.yaml keys (+ `model_dir`).  examples: list of {"audio": array, "text": str};
-    defaults to a seeded synthetic set (no hub access here).  Serves both model types, like the reference's
+    """config: evaluation.yaml keys (+ `model_dir`).  examples: list of {"audio": array, "text": str} and optionally
+    "sampling_rate" (an example without one is at `config.sampling_rate`, the target; another rate is resampled on the
+    GPU); defaults to a seeded synthetic set (no hub access here).  Serves both model types, like the reference's
     pipeline-based `evaluate` (R/src/coral/evaluate.py:29-85, :123-158)."""
     from .config import DictConfig
 
@@ -301,6 +314,9 @@ def evaluate(config, examples: list | None = None) -> dict:
     saved = setup.load_saved() if mtype == "whisper" else setup.load_saved(no_lm=bool(config.get("no_lm", False)))
     model, processor = saved.model, saved.processor
     id_rows = timed = None
+    rates = None  # one per example when any of them names a rate
+    if examples is not None and any(e.get("sampling_rate") is not None for e in examples):
+        rates = [e.get("sampling_rate") for e in examples]
     if mtype == "whisper":
         if examples is None:
             import numpy as np
@@ -321,7 +337,8 @@ def evaluate(config, examples: list | None = None) -> dict:
                                             sample_seed=int(config.get("sample_seed", 0) or 0),
                                             prompt_ids=_ids(config.get("prompt_ids", None)),
                                             condition_on_prev_tokens=bool(config.get("condition_on_prev_tokens", False) or False),
-                                            prompt_condition_type=config.get("prompt_condition_type", None))
+                                            prompt_condition_type=config.get("prompt_condition_type", None),
+                                            sampling_rate=rates)
         if preds and isinstance(preds[0], dict):
             timed, preds = preds, [p["text"] for p in preds]
     else:
@@ -331,7 +348,7 @@ def evaluate(config, examples: list | None = None) -> dict:
                                                      min(3.0, config.max_seconds_per_example), config.sampling_rate)]
         preds = transcribe(model, processor, [e["audio"] for e in examples], config.batch_size,
                            chunk_length_s=chunk_length_s, stride_length_s=config.get("stride_length_s", None),
-                           timestamp_source=config.get("timestamp_source", "emission"))
+                           timestamp_source=config.get("timestamp_source", "emission"), sampling_rate=rates)
     preds = [p.lower().strip() for p in preds]
     labels = [e["text"].lower().strip() if config.lower_case else e["text"].strip() for e in examples]
     scores = dict(model_type=mtype, n=len(examples))

@@ -78,6 +78,7 @@ class TrainingArgs:
     normalise_audio: bool = True
     augment_audio: bool = True
     device_input_pipeline: bool = True
+    max_source_sampling_rate: int | None = None  # raw audio up to this rate is resampled on the device; None: none is
     zero_stage: int = 0   # >0: optimiser state + update sharded over the ranks (the reference's `--zero-stage 2` launch)
     # "sum": the micro-batches of an optimiser step are NOT scaled by 1 / gradient_accumulation_steps - what the
     # reference's transformers.Trainer (>= 4.46; pinned 5.5.0) does for Wav2Vec2ForCTC / WhisperForConditionalGeneration
@@ -139,6 +140,8 @@ def _training_args(config, learning_rate) -> TrainingArgs:
         padding=config.padding if isinstance(config.padding, str) else "longest",
         augment_audio=bool(config.get("augment_audio", True)), normalise_audio=bool(config.get("normalise_audio", True)),
         device_input_pipeline=bool(config.get("device_input_pipeline", True)),
+        max_source_sampling_rate=(int(config.get("max_source_sampling_rate"))
+                                  if config.get("max_source_sampling_rate", None) is not None else None),
         zero_stage=int(config.get("zero_stage", 0) or 0))
 
 

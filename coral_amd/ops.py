@@ -478,6 +478,27 @@ def pcm_prepare(pcm, lengths, y, mask, B, N, ld_in, peak_normalize=False, zero_m
                                int(peak_normalize), int(zero_mean_unit_var), eps, _stream()), "ca_pcm_prepare")
 
 
+def resample(pcm, len_in, rows, R, taps, off, O, Nw, K, y, len_out, route=0):
+    """ca_resample: rows `rows` (int32 device tensor, or None for 0..R-1) of the int16 / fp32 batch `pcm` through the
+    polyphase table (taps fp32 [Nw, K], off int32 [Nw], device) into the fp32 rows of `y`, with their lengths in
+    `len_out`.  route 0 picks by size, 1 stages the table in LDS, 2 reads it from global memory."""
+    if pcm.dtype not in (torch.int16, torch.float32):
+        raise CoralAmdError("resample: PCM must be int16 or float32")
+    if y.dtype != torch.float32 or taps.dtype != torch.float32:
+        raise CoralAmdError("resample: the output and the taps must be float32")
+    for name, t in (("len_in", len_in), ("len_out", len_out), ("off", off)) + ((("rows", rows),) if rows is not None else ()):
+        if t.dtype != torch.int32:
+            raise CoralAmdError(f"resample: {name} must be int32")
+    if taps.numel() < Nw * K or off.numel() < Nw:
+        raise CoralAmdError(f"resample: a table of {taps.numel()} taps and {off.numel()} offsets for Nw = {Nw}, K = {K}")
+    if rows is not None and rows.numel() < R:
+        raise CoralAmdError(f"resample: {rows.numel()} row indices for R = {R}")
+    if pcm.dim() != 2 or y.dim() != 2 or not pcm.is_contiguous() or not y.is_contiguous():
+        raise CoralAmdError("resample: the batch and the output must be contiguous [rows, samples] tensors")
+    check(lib().ca_resample(_p(pcm), int(pcm.dtype == torch.int16), pcm.shape[1], _p(len_in), _p(rows), R, _p(taps), _p(off),
+                            O, Nw, K, _p(y), y.shape[1], _p(len_out), route, _stream()), "ca_resample")
+
+
 def wave_scale(x, scale, y, B, N):
     check(lib().ca_wave_scale(_p(x), _p(scale), _p(y), B, N, _stream()), "ca_wave_scale")
 

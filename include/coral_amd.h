@@ -335,6 +335,41 @@ int ca_frame_lengths(const int32_t* attention_mask, int32_t B, int64_t N, const 
 int ca_pcm_prepare(const void* pcm, int32_t is_int16, int64_t ld_in, const int32_t* lengths, float* y,
                    int32_t* mask, int32_t B, int64_t N, int32_t peak_normalize, int32_t zero_mean_unit_var,
                    float eps, void* stream);
+/* ca_resample: audio at any sampling rate -> the model's rate, in front of ca_pcm_prepare (the reference's
+ *   `dataset.cast_column("audio", Audio(sampling_rate=...))`, R/src/coral/data.py).  A band-limited windowed-sinc
+ *   interpolator at the rational ratio Nw / O (g = gcd(src, dst), O = src / g, Nw = dst / g); with
+ *   s = rolloff * min(1, Nw / O) and L the filter width in zero crossings,
+ *     y[n] = sum over the integers m with |(m - n O / Nw) s| < L of
+ *            x[m] * s * sinc((m - n O / Nw) s) * cos^2(pi (m - n O / Nw) s / (2 L)),   sinc(t) = sin(pi t) / (pi t),
+ *   x[m] = 0 outside [0, len); n_out = ceil(Nw * len / O); no renormalisation of the DC gain (the formula of
+ *   torchaudio.functional.resample's sinc_interp_hann without its all-zero taps).  The host builds the polyphase
+ *   table in float64 (coral_amd/resample.py): phase i = n mod Nw, off[i] the first m of its support, taps[i][k] the
+ *   tap at m = off[i] + k, rows zero-padded to K;  y[j Nw + i] = sum_k taps[i][k] * x[j O + off[i] + k], accumulated
+ *   in fp32 in the order k = 0, 1, ..., K - 1 (first product, then fmaf): no atomics, the same bits on every route
+ *   and run.
+ *   pcm: int16 (is_int16 != 0, scaled by 1/32768) or fp32 rows of ld_in samples; len_in int32 per row (clamped to
+ *   [0, ld_in]).  rows: int32 [R] on the device, the rows of pcm / len_in / y / len_out this launch serves (NULL =
+ *   rows 0 .. R-1); a row not named is not touched, nor is its len_out: a batch with several source rates takes one
+ *   launch per distinct rate into one output buffer.  taps fp32 [Nw, K], off int32 [Nw], on the device.
+ *   y fp32 rows of ld_out: y[row, n] for n < len_out[row] = min(n_out, ld_out), 0 from there to ld_out.  Samples at or
+ *   beyond len_in[row] are masked, never read as values.  The identity plan (O = Nw = K = 1, tap 1, off 0) is an exact
+ *   copy (int16 -> float exactly).  All index arithmetic is 64-bit.
+ *   One workgroup computes CA_RESAMPLE_CHUNK consecutive outputs of one row from an LDS window of the input span they
+ *   need (ceil(CHUNK * O / Nw) + K + 1 samples).  route 1: the table is staged in LDS beside the window (row stride
+ *   K | 1); route 2: it is read from global memory (44 100 -> 16 000 Hz at L = 32 is 114 560 B and fits beside its
+ *   window, 11 025 -> 16 000 Hz at L = 32 is 166 400 B and does not: the global route is not optional); route 0:
+ *   route 1 where window and table fit CA_RESAMPLE_LDS_BYTES (never slower where both were measured),
+ *   else route 2.
+ *   CA_ERR_ARG: a null pointer, R / O / Nw / K < 1, ld_in / ld_out < 1, K > CA_RESAMPLE_MAX_TAPS,
+ *   Nw * K > CA_RESAMPLE_MAX_TABLE, a route outside 0..2, a window that does not fit CA_RESAMPLE_LDS_BYTES (O / Nw too
+ *   large), route 1 with a table that does not fit beside it. */
+#define CA_RESAMPLE_CHUNK 1024
+#define CA_RESAMPLE_MAX_TAPS 4096
+#define CA_RESAMPLE_MAX_TABLE (1 << 20)
+#define CA_RESAMPLE_LDS_BYTES 163840
+int ca_resample(const void* pcm, int32_t is_int16, int64_t ld_in, const int32_t* len_in, const int32_t* rows,
+                int32_t R, const float* taps, const int32_t* off, int32_t O, int32_t Nw, int32_t K, float* y,
+                int64_t ld_out, int32_t* len_out, int32_t route, void* stream);
 /* ------------------------------------------------------------------------------------
  * On-device waveform augmentation (the chain torch_audiomentations builds at
  * R/src/coral/data.py:708-738: Gain, AddBackgroundNoise, AddColoredNoise, Band/High/Low-pass, BandStop).

@@ -290,15 +290,25 @@ def evaluate(config, examples: list | None = None) -> dict:
     pipeline-based `evaluate` (R/src/coral/evaluate.py:29-85, :123-158)."""
     from .config import DictConfig
 
-    from .error_rates import batch_scores, check_options, score_table
+    from .error_rates import BOOTSTRAP_FIELDS, batch_scores, bootstrap_rates, check_options, score_table
 
     categories = list(config.get("score_categories", None) or [])
     normalise = bool(config.get("normalise_error_rates", False) or False)
-    on_device = check_options(config.get("error_rates", "host"), normalise, categories)
+    boot_cluster = config.get("bootstrap_cluster", None)
+    boot = None  # bootstrap_samples: null leaves every output below as it is without the key
+    if config.get("bootstrap_samples", None) is not None:
+        confidence = config.get("bootstrap_confidence", None)
+        boot = dict(n_resamples=int(config.bootstrap_samples), seed=int(config.get("bootstrap_seed", 0) or 0),
+                    confidence=0.95 if confidence is None else float(confidence))
+    on_device = check_options(config.get("error_rates", "host"), normalise, categories,
+                              None if boot is None else boot["n_resamples"], None if boot is None else boot["confidence"],
+                              boot_cluster)
     for i, e in enumerate(examples or []):  # before anything is transcribed
         for c in categories:
             if c not in e:
                 raise ValueError(f"score_categories: example {i} has no {c!r}")
+        if boot_cluster is not None and boot_cluster not in e:
+            raise ValueError(f"bootstrap_cluster: example {i} has no {boot_cluster!r}")
     model_dir = config.get("model_dir", config.model_id)
     mtype = saved_model_type(model_dir)
     chunk_length_s = config.get("chunk_length_s", 0) or 0
@@ -354,17 +364,27 @@ def evaluate(config, examples: list | None = None) -> dict:
     scores = dict(model_type=mtype, n=len(examples))
     table = None
     if any(labels) and on_device:  # the same two rates from alignment counts (ca_edit_counts), and what only counts give
-        res = batch_scores(preds, labels, normalise, model.engine.device if hasattr(model, "engine") else "cuda")
+        device = model.engine.device if hasattr(model, "engine") else "cuda"
+        res = batch_scores(preds, labels, normalise, device)
         scores.update(cer=res["cer"], wer=res["wer"],
                       error_counts=dict(char=res["char_counts"].sum(0).tolist(), word=res["word_counts"].sum(0).tolist()))
+        if boot is not None:  # the published form: mean ± half_width of the resampled rates (ca_bootstrap_sums)
+            if boot_cluster is not None:
+                missing = [i for i, e in enumerate(examples) if boot_cluster not in e]
+                if missing:
+                    raise ValueError(f"bootstrap_cluster: example {missing[0]} has no {boot_cluster!r}")
+                boot["clusters"] = [e[boot_cluster] for e in examples]
+            scores["bootstrap"] = dict(bootstrap_rates(res["char_counts"], res["word_counts"], normalise, device=device, **boot),
+                                       n_resamples=boot["n_resamples"], seed=boot["seed"], confidence=boot["confidence"])
         if categories:
-            table = scores["score_table"] = score_table(examples, categories, res["char_counts"], res["word_counts"], normalise)
+            table = scores["score_table"] = score_table(examples, categories, res["char_counts"], res["word_counts"], normalise,
+                                                        bootstrap=None if boot is None else dict(boot, device=device))
     elif any(labels):  # CER / WER need reference texts (a synthetic Whisper set has none: ids-only output)
         scores.update(cer=cer(preds, labels), wer=wer(preds, labels))
     name = str(config.model_id).replace("/", "--") + "." + str(config.dataset).split("::")[0].replace("/", "--")
     if config.store_results and table is not None:
         with Path(f"{name}.scores.csv").open("w", newline="") as f:
-            w = csv.DictWriter(f, fieldnames=categories + ["cer", "wer"])
+            w = csv.DictWriter(f, fieldnames=categories + ["cer", "wer"] + (list(BOOTSTRAP_FIELDS) if boot is not None else []))
             w.writeheader()
             w.writerows(table)
         scores["scores_csv"] = f"{name}.scores.csv"

@@ -696,6 +696,58 @@ def edit_counts(ref, ref_off, hyp, hyp_off, device="cuda", route=0, order=None):
     return edit_counts_launch(edit_counts_plan(ref, ref_off, hyp, hyp_off, device, route, order))
 
 
+def bootstrap_sums(vals, members, goff, R, seed=0, device="cuda"):
+    """Bootstrap column sums (ca_bootstrap_sums): vals int [N, C] >= 0 (C a multiple of 4, at most
+    CA_BOOTSTRAP_MAX_COLUMNS), groups in CSR form (members: example indices laid end to end; goff int64 [G + 1]), R
+    replicates, a 64-bit seed; all host arrays, checked here, where they start, as `edit_counts_plan` checks its own.
+    One upload, one launch, one copy back.  -> sums int64 [G, R, C], a host array."""
+    import numpy as np
+
+    vals = np.asarray(vals)
+    if vals.ndim != 2 or not np.issubdtype(vals.dtype, np.integer):
+        raise ValueError(f"bootstrap_sums: vals must be an integer array [N, C], got {vals.dtype} {list(vals.shape)}")
+    N, Cn = vals.shape
+    if N < 1 or Cn < 4 or Cn > _lib.BOOTSTRAP_MAX_COLUMNS or Cn % 4:
+        raise ValueError(f"bootstrap_sums: vals [N = {N}, C = {Cn}] needs N >= 1 and C a multiple of 4 in 4 .. "
+                         f"{_lib.BOOTSTRAP_MAX_COLUMNS} (CA_BOOTSTRAP_MAX_COLUMNS)")
+    if int(vals.min()) < 0 or int(vals.max()) >= 1 << 31:
+        raise ValueError("bootstrap_sums: values must lie in [0, 2^31)")
+    members_in, goff_in = np.asarray(members).reshape(-1), np.asarray(goff).reshape(-1)
+    G, R, seed = len(goff_in) - 1, int(R), int(seed)
+    if G < 1:
+        raise ValueError(f"bootstrap_sums: goff must hold G + 1 >= 2 offsets, got {len(goff_in)}")
+    goff = np.ascontiguousarray(goff_in, dtype=np.int64)
+    if goff[0] != 0 or goff[-1] != len(members_in) or bool((np.diff(goff) < 0).any()):
+        raise ValueError(f"bootstrap_sums: goff must start at 0, not decrease and end at the {len(members_in)} members")
+    sizes = np.diff(goff)
+    if int(sizes.min()) < 1:
+        raise ValueError(f"bootstrap_sums: group {int(sizes.argmin())} is empty")
+    if int(sizes.max()) > _lib.BOOTSTRAP_MAX_GROUP:
+        raise ValueError(f"bootstrap_sums: group {int(sizes.argmax())} has {int(sizes.max())} members, the limit is "
+                         f"{_lib.BOOTSTRAP_MAX_GROUP} (CA_BOOTSTRAP_MAX_GROUP)")
+    if int(members_in.min()) < 0 or int(members_in.max()) >= N:
+        bad = int(np.flatnonzero((members_in < 0) | (members_in >= N))[0])
+        raise ValueError(f"bootstrap_sums: member {bad} is {int(members_in[bad])}, outside [0, {N})")
+    if R < 1 or G * R >= 1 << 32:
+        raise ValueError(f"bootstrap_sums: R = {R} must be at least 1 and G * R = {G * R} below 2^32")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"bootstrap_sums: seed {seed} is not an unsigned 64-bit integer")
+    # one buffer, one copy: offsets (int64) first, then the rows (16-byte aligned: G + 1 is padded to even), then members
+    parts = [goff, np.zeros((G + 1) % 2, dtype=np.int64), np.ascontiguousarray(vals, dtype=np.int32).reshape(-1),
+             np.ascontiguousarray(members_in, dtype=np.int32)]
+    at, pos = [], 0
+    for a in parts:
+        at.append(pos)
+        pos += a.nbytes
+    dev = torch.from_numpy(np.concatenate([a.view(np.uint8) for a in parts])).to(device)
+    sums = torch.empty(G, R, Cn, dtype=torch.int64, device=dev.device)
+    base = _p(dev)
+    with torch.cuda.device(dev.device):
+        check(lib().ca_bootstrap_sums(base + at[2], N, Cn, base + at[3], len(members_in), base + at[0], G, R, seed, _p(sums),
+                                      _stream()), "ca_bootstrap_sums")
+    return sums.cpu().numpy()
+
+
 def mask_frames(h, tmask, fmask, embed, flen, B, T, Cn):
     check(lib().ca_mask_frames(_p(h), _p(tmask), _p(fmask), _p(embed), _p(flen), B, T, Cn,
                                _stream()), "ca_mask_frames")

@@ -697,6 +697,33 @@ int ca_edit_counts(const int32_t* ref, const int64_t* ref_off, const int32_t* hy
                    void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Bootstrap resampling of per-example counts (coral_amd/error_rates.py; csrc/bootstrap.hip): for every group g of
+ * examples and every replicate r, the column sums of n_g rows of `vals` drawn with replacement from the group.
+ *   vals int32 [N, C] row-major, every value >= 0, 16-byte aligned; C a multiple of 4, 4 <= C <= CA_BOOTSTRAP_MAX_COLUMNS
+ *   (one system's row is char errors, char denominator, word errors, word denominator: one 16-byte load; the caller
+ *   pads).  Groups in CSR form: members int32 [n_members] holds example indices in [0, N), goff int64 [G + 1] starts at
+ *   0, does not decrease and ends at n_members; group g owns members[goff[g] .. goff[g + 1]), n_g of them,
+ *   1 <= n_g <= CA_BOOTSTRAP_MAX_GROUP.  Groups may overlap and list their members in any order.  1 <= R, G * R < 2^32.
+ *   sums int64 [G, R, C], 16-byte aligned:  sums[g, r, :] = sum over j < n_g of vals[members[goff[g] + k(g, r, j)], :],
+ *       idx = ((uint64)(g * R + r) << 32) | j;   u = ca_hash32(seed, idx)  (csrc/common.h);   k = ((uint64)u * n_g) >> 32.
+ *   The draw depends on (seed, g, r, j) alone: every column of a replicate sees the same draws, so systems stacked side
+ *   by side in `vals` are compared on the same resamples (a paired comparison).  The floor maps 2^32 hash values onto
+ *   n_g members, so a member's probability differs from 1 / n_g by at most 2^-32: a relative error of at most
+ *   n_g * 2^-32 <= 2^-8 at the group limit, which is why n_g is capped at 2^24 (and far below the resampling noise at
+ *   any R that fits the call).
+ *   The values live on the device, so the call cannot check them; coral_amd/ops.py does, on the host, before the upload.
+ *   Behind the C entry the kernel still reads nothing through an unchecked index: a group whose offsets are not as above
+ *   gets -1 in all C columns of all its replicates and touches no memory, and a member outside [0, N) adds nothing.
+ *   Exact integers, no atomics, no LDS: bit-identical from run to run.  One launch, no allocation, no synchronisation;
+ *   bad arguments (a null pointer, a misaligned vals / sums, C outside its set, N, n_members, G or R < 1,
+ *   G * R >= 2^32) return CA_ERR_ARG with the function's name in ca_last_error().
+ * ---------------------------------------------------------------------------------- */
+#define CA_BOOTSTRAP_MAX_COLUMNS 32
+#define CA_BOOTSTRAP_MAX_GROUP (1 << 24)
+int ca_bootstrap_sums(const int32_t* vals, int32_t N, int32_t C, const int32_t* members, int64_t n_members,
+                      const int64_t* goff, int32_t G, int64_t R, uint64_t seed, int64_t* sums, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Small elementwise pieces of the wav2vec2 encoder.
  * ca_mask_frames: SpecAugment + padding ($TF/.../modeling_wav2vec2.py:1272-1316, 752-755):
  *   h[b,t,:] = embed where tmask[b,t]; h[b,t,c] = 0 where fmask[b,c]; h[b,t,:] = 0 for

@@ -188,6 +188,7 @@ EDIT_MAX_TOKENS = (1 << 20) - 1  # CA_EDIT_MAX_TOKENS
 EDIT_WAVE_MAX = 1024  # CA_EDIT_WAVE_MAX
 EDIT_PANEL = 2048  # CA_EDIT_PANEL
 BOOTSTRAP_MAX_COLUMNS, BOOTSTRAP_MAX_GROUP = 32, 1 << 24  # CA_BOOTSTRAP_*
+CHUNK_MERGE_MAX_TOKENS = 1024  # CA_CHUNK_MERGE_MAX_TOKENS
 RESAMPLE_CHUNK, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_TABLE = 1024, 4096, 1 << 20  # CA_RESAMPLE_*
 RESAMPLE_LDS_BYTES = 163840  # CA_RESAMPLE_LDS_BYTES
 KMAJOR, MNMAJOR = 0, 1
@@ -281,6 +282,7 @@ SIGNATURES = {
     "ca_edit_counts_workspace_bytes": (_i64, [_i32, _i64, _i64]),
     "ca_edit_counts": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i64, _vp]),
     "ca_bootstrap_sums": (C.c_int, [_vp, _i32, _i32, _vp, _i64, _vp, _i32, _i64, _u64, _vp, _vp]),
+    "ca_overlap_merge": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp]),
     "ca_beam_select_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "ca_beam_select": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ca_beam_advance": (C.c_int, [C.POINTER(CaBeamDesc), _vp]),

@@ -23,6 +23,12 @@ from .model_setup import load_model_setup
 
 logger = logging.getLogger(__package__)
 
+WHISPER_CHUNK_LENGTH_REFUSAL = (
+    "chunk_length_s > 0 is built for wav2vec2 models and for Whisper's chunked long-form mode only: with "
+    "whisper_long_form: sequential a Whisper model transcribes recordings longer than 30 s without it (transformers' "
+    "sequential long-form decoding): set chunk_length_s to 0, or set whisper_long_form: chunked (the pipeline's "
+    "overlapping chunks, decoded as batches and merged on the GPU)")
+
 
 def transcribe(model, processor, arrays: list, batch_size: int = 16, chunk_length_s: float = 0, stride_length_s=None,
                return_timestamps=None, timestamp_source: str = "emission", sampling_rate=None):
@@ -88,7 +94,7 @@ def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max
                        num_beams: int = 1, return_timestamps: bool = False, temperature=None, logprob_threshold=None,
                        compression_ratio_threshold=None, no_speech_threshold=None, sample_seed: int = 0, prompt_ids=None,
                        condition_on_prev_tokens=None, prompt_condition_type=None, prompt: str | None = None,
-                       sampling_rate=None):
+                       sampling_rate=None, long_form: str = "sequential", chunk_length_s=None, stride_length_s=None):
     """The Whisper branch of the ASR pipeline ($TF/pipelines/automatic_speech_recognition.py:345,529,600): pad / trim
     every clip to 30 s, log-mel on the GPU, `model.generate(input_features, language="danish", task="transcribe")`
     (R/src/coral/evaluate.py:56-60), decode the generated ids without special tokens.
@@ -113,9 +119,30 @@ def transcribe_whisper(model, processor, arrays: list, batch_size: int = 16, max
     place of prompt_ids, through the processor's (or its tokenizer's) `get_prompt_ids`.  With the fallback arguments a
     window accepted at a temperature of 0.5 or more leaves the next one unconditioned.  Not with beams, not with "word".
     sampling_rate: the rate of `arrays`, one int or one per recording (None: the extractor's).  Recordings at another
-    rate are resampled on the GPU first (coral_amd/resample.py); the 30 s rule then applies to the resampled audio."""
+    rate are resampled on the GPU first (coral_amd/resample.py); the 30 s rule then applies to the resampled audio.
+    long_form="chunked": the pipeline's `chunk_length_s` mode instead of the sequential loop (coral_amd/chunked_whisper.py):
+    every recording is cut into overlapping chunks of chunk_length_s seconds (0 / None: 30; stride_length_s as in
+    `transcribe`), the chunks of all recordings are decoded as batches of batch_size and merged on the GPU
+    (`ca_overlap_merge`); the id rows are then the merged text ids.  Greedy or beams (beams without timestamps); "word",
+    the fallback and the prompt arguments are refused by name.  long_form="sequential" (the default) is everything
+    above, unchanged, and still refuses chunk_length_s > 0."""
     from .resample import to_rate
 
+    if long_form not in ("sequential", "chunked"):
+        raise ValueError(f"long_form must be \"sequential\" or \"chunked\", got {long_form!r}")
+    if long_form == "chunked":
+        from .chunked_whisper import transcribe_chunked
+
+        res = transcribe_chunked(model, processor, arrays, chunk_length_s or 30.0, stride_length_s, batch_size, max_length,
+                                 num_beams or 1, return_timestamps, sampling_rate, temperature=temperature,
+                                 logprob_threshold=logprob_threshold, compression_ratio_threshold=compression_ratio_threshold,
+                                 no_speech_threshold=no_speech_threshold, prompt_ids=prompt_ids, prompt=prompt,
+                                 condition_on_prev_tokens=condition_on_prev_tokens, prompt_condition_type=prompt_condition_type)
+        if return_timestamps:
+            return [dict(text=r["text"], chunks=r["chunks"]) for r in res], [r["ids"] for r in res]
+        return [r["text"] for r in res], [r["ids"] for r in res]
+    if chunk_length_s:
+        raise ValueError(WHISPER_CHUNK_LENGTH_REFUSAL)
     model.eval()
     if prompt is not None:
         getter = getattr(processor, "get_prompt_ids", None) or getattr(getattr(processor, "tokenizer", None), "get_prompt_ids", None)
@@ -312,10 +339,23 @@ def evaluate(config, examples: list | None = None) -> dict:
     model_dir = config.get("model_dir", config.model_id)
     mtype = saved_model_type(model_dir)
     chunk_length_s = config.get("chunk_length_s", 0) or 0
-    if mtype == "whisper" and chunk_length_s > 0:
-        raise ValueError("chunk_length_s > 0 is built for wav2vec2 models only: a Whisper model transcribes recordings "
-                         "longer than 30 s without it (transformers' sequential long-form decoding; the pipeline's chunked "
-                         "merge is not built): set chunk_length_s to 0")
+    long_form = config.get("whisper_long_form", None) or "sequential"
+    if mtype == "whisper" and long_form not in ("sequential", "chunked"):
+        raise ValueError(f"whisper_long_form must be sequential or chunked, got {long_form!r}")
+    if mtype == "whisper" and chunk_length_s > 0 and long_form != "chunked":
+        raise ValueError(WHISPER_CHUNK_LENGTH_REFUSAL)
+    if mtype == "whisper" and long_form == "chunked":  # what the mode refuses, before the model is loaded
+        from .chunked_whisper import check_chunked_arguments
+
+        check_chunked_arguments(chunk_length_s or 30.0, config.get("num_beams", 1) or 1,
+                                _whisper_timestamp_mode(config.get("return_timestamps", False)),
+                                dict(temperature=_plain(config.get("temperature", None)),
+                                     logprob_threshold=config.get("logprob_threshold", None),
+                                     compression_ratio_threshold=config.get("compression_ratio_threshold", None),
+                                     no_speech_threshold=config.get("no_speech_threshold", None),
+                                     prompt_ids=_ids(config.get("prompt_ids", None)),
+                                     condition_on_prev_tokens=bool(config.get("condition_on_prev_tokens", False) or False),
+                                     prompt_condition_type=config.get("prompt_condition_type", None)))
     mcfg = DictConfig(model=DictConfig(type=mtype, sampling_rate=config.sampling_rate, decoder=None),
                       model_dir=model_dir, padding="longest",
                       max_seconds_per_example=config.max_seconds_per_example)
@@ -348,7 +388,8 @@ def evaluate(config, examples: list | None = None) -> dict:
                                             prompt_ids=_ids(config.get("prompt_ids", None)),
                                             condition_on_prev_tokens=bool(config.get("condition_on_prev_tokens", False) or False),
                                             prompt_condition_type=config.get("prompt_condition_type", None),
-                                            sampling_rate=rates)
+                                            sampling_rate=rates, long_form=long_form, chunk_length_s=chunk_length_s,
+                                            stride_length_s=config.get("stride_length_s", None))
         if preds and isinstance(preds[0], dict):
             timed, preds = preds, [p["text"] for p in preds]
     else:

@@ -748,6 +748,74 @@ def bootstrap_sums(vals, members, goff, R, seed=0, device="cuda"):
     return sums.cpu().numpy()
 
 
+def skip_bitmap(skip_ids, n_bits: int, device="cuda"):
+    """The skip bitmap of ca_overlap_merge: bit `id` set for every id in skip_ids (all in [0, n_bits)) -> int32 words on
+    the device (the kernel reads them as uint32)."""
+    import numpy as np
+
+    n_bits = int(n_bits)
+    ids = np.asarray(sorted(set(int(t) for t in skip_ids)), dtype=np.int64)
+    if n_bits < 1 or (len(ids) and (int(ids[0]) < 0 or int(ids[-1]) >= n_bits)):
+        raise ValueError(f"skip_bitmap: ids must lie in [0, n_bits = {n_bits})")
+    words = np.zeros((n_bits + 31) // 32, dtype=np.uint32)
+    np.bitwise_or.at(words, ids >> 5, (np.uint32(1) << (ids & 31).astype(np.uint32)))
+    return dict(words=torch.from_numpy(words.view(np.int32)).to(device), n_bits=n_bits)
+
+
+def overlap_merge(ids, row_len, group_off, row_start=None, skip=None, want_cuts=False):
+    """Overlap merge of token rows (ca_overlap_merge): ids int32 [rows, ld] on the device; row_len, row_start (None: 0)
+    and group_off (G + 1 offsets into the rows) host arrays, checked here, where they start; skip: a `skip_bitmap` or
+    None.  One upload of the offsets, one launch.  -> dict(buf: int32 device buffer holding out | out_len | cuts in that
+    order, out_off: host int64 [G + 1], G, rows): `overlap_merge_read` copies it back once."""
+    import numpy as np
+
+    if ids.dtype != torch.int32 or ids.dim() != 2 or not ids.is_contiguous():
+        raise ValueError(f"overlap_merge: ids must be a contiguous int32 [rows, ld] tensor, got {ids.dtype} {list(ids.shape)}")
+    rows, ld = ids.shape
+    row_len = np.ascontiguousarray(row_len, dtype=np.int64).reshape(-1)
+    row_start = np.zeros(rows, dtype=np.int64) if row_start is None else np.ascontiguousarray(row_start, dtype=np.int64).reshape(-1)
+    group_off = np.ascontiguousarray(group_off, dtype=np.int64).reshape(-1)
+    G = len(group_off) - 1
+    if rows < 1 or ld < 1 or len(row_len) != rows or len(row_start) != rows:
+        raise ValueError(f"overlap_merge: ids [{rows}, {ld}] needs one row_len and one row_start per row, got {len(row_len)} "
+                         f"and {len(row_start)}")
+    if G < 1 or group_off[0] != 0 or group_off[-1] != rows or bool((np.diff(group_off) < 0).any()):
+        raise ValueError(f"overlap_merge: group_off must hold G + 1 >= 2 offsets, start at 0, not decrease and end at the {rows} rows")
+    if int(row_len.min()) < 0 or int(row_start.min()) < 0 or int((row_start + row_len).max()) > ld:
+        bad = int(np.flatnonzero((row_len < 0) | (row_start < 0) | (row_start + row_len > ld))[0])
+        raise ValueError(f"overlap_merge: row {bad} (start {int(row_start[bad])}, length {int(row_len[bad])}) leaves [0, ld = {ld}]")
+    out_off = np.concatenate([[0], np.cumsum(row_len)])[group_off]  # a group's capacity: the sum of its row lengths
+    cap = int(out_off[-1])
+    if cap >= 1 << 31:
+        raise ValueError(f"overlap_merge: {cap} tokens in all, the limit is 2^31 - 1")
+    dev = ids.device
+    args = torch.from_numpy(np.concatenate([row_start, row_len, group_off, out_off]).astype(np.int32)).to(dev)
+    n_cuts = 2 * rows if want_cuts else 0
+    buf = torch.empty(max(1, cap) + G + n_cuts, dtype=torch.int32, device=dev)
+    cap_alloc = max(1, cap)
+    with torch.cuda.device(dev):
+        check(lib().ca_overlap_merge(_p(ids), ld, _p(args), _p(args, rows), rows, int(row_len.max()),
+                                     None if skip is None else _p(skip["words"]), 0 if skip is None else skip["n_bits"],
+                                     _p(args, 2 * rows), _p(args, 2 * rows + G + 1), G, _p(buf), cap_alloc,
+                                     _p(buf, cap_alloc), _p(buf, cap_alloc + G) if want_cuts else None, _stream()),
+              "ca_overlap_merge")
+    return dict(buf=buf, out_off=out_off, cap=cap_alloc, G=G, rows=rows, want_cuts=bool(want_cuts))
+
+
+def overlap_merge_read(res):
+    """One device-to-host copy of an `overlap_merge` result -> (merged id list per group, out_len array, cuts int32
+    [rows, 2] or None).  A group the kernel refused (out_len -1) raises."""
+    host = res["buf"].cpu().numpy()
+    cap, G, rows = res["cap"], res["G"], res["rows"]
+    out_len = host[cap:cap + G]
+    if len(out_len) and int(out_len.min()) < 0:
+        raise CoralAmdError(f"ca_overlap_merge: group {int(out_len.argmin())} was refused by the kernel (offsets or rows out of range)")
+    off = res["out_off"]
+    merged = [host[int(off[g]):int(off[g]) + int(out_len[g])].tolist() for g in range(G)]
+    cuts = host[cap + G:cap + G + 2 * rows].reshape(rows, 2) if res["want_cuts"] else None
+    return merged, out_len, cuts
+
+
 def mask_frames(h, tmask, fmask, embed, flen, B, T, Cn):
     check(lib().ca_mask_frames(_p(h), _p(tmask), _p(fmask), _p(embed), _p(flen), B, T, Cn,
                                _stream()), "ca_mask_frames")

@@ -336,7 +336,12 @@ class WhisperForConditionalGeneration:
                 return rows
             return rows, [dict(skipped=bool(sk), **{a: v for a, v in k.items() if a != "row"}) for k, sk in zip(kept, skipped)]
         return self.engine.generate(input_features, prefix, max_length, suppress_tokens=None,
-                                    begin_suppress_tokens=[220, self.shape.eos_token_id], **kw)
+                                    begin_suppress_tokens=self.begin_suppress(), **kw)
+
+    def begin_suppress(self) -> list[int]:
+        """The begin-suppress set: blank ' ' = 220 and eos.  An id the vocabulary does not hold is left out (a toy
+        vocabulary of fewer than 221 ids has no 220 to suppress; the mask has one entry per id)."""
+        return [t for t in (220, self.shape.eos_token_id) if t < self.shape.vocab_size]
 
     def prompt_policy(self, prompt_ids=None, condition_on_prev_tokens=None, prompt_condition_type=None):
         """The PromptPolicy of these generate arguments, or None where they leave decoding as it is.  <|startofprev|> is
@@ -361,7 +366,7 @@ class WhisperForConditionalGeneration:
             kw = dict(return_timestamps=True, timestamp_begin=self.forced_prefix()[-1] + 1,
                       max_initial_timestamp_index=self.generation_config.get("max_initial_timestamp_index", None))
         return self.engine.generate(input_features, None, int(inputs["max_length"]), suppress_tokens=None,
-                                    begin_suppress_tokens=[220, s.eos_token_id],
+                                    begin_suppress_tokens=self.begin_suppress(),
                                     prefix_rows=torch.tensor(inputs["rows"], dtype=torch.int64),
                                     prefix_start=torch.tensor(inputs["start"], dtype=torch.int32), cross_kv=cross_kv,
                                     no_speech_index=int(inputs.get("no_speech_index", 0)), **kw, **scoring)
@@ -404,7 +409,7 @@ class WhisperForConditionalGeneration:
                 return self.prompted_window(None, inputs, return_timestamps, cross_kv=kv, temperature=float(temperature),
                                             sample_uniforms=uniforms, return_stats=True, no_speech_token=policy.no_speech_token)
             return eng.generate(None, prefix, max_length, suppress_tokens=None,
-                                begin_suppress_tokens=[220, s.eos_token_id], temperature=float(temperature),
+                                begin_suppress_tokens=self.begin_suppress(), temperature=float(temperature),
                                 sample_uniforms=uniforms, return_stats=True, no_speech_token=policy.no_speech_token,
                                 cross_kv=kv, **kw)
 

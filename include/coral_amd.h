@@ -724,6 +724,39 @@ int ca_bootstrap_sums(const int32_t* vals, int32_t N, int32_t C, const int32_t* 
                       const int64_t* goff, int32_t G, int64_t R, uint64_t seed, int64_t* sums, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Overlap merge of token sequences (coral_amd/chunked_whisper.py; csrc/chunk_merge.hip): the chunks of a long Whisper
+ * recording overlap in audio; their token sequences are merged where they overlap in text, as transformers'
+ * `_find_longest_common_sequence` merges them.  For the sequences s_0 .. s_{n-1} of one group (its rows in order):
+ *   left = s_0; for every next sequence `right` (L = len(left), R = len(right)):
+ *     for i = 1 .. L + R - 1:  a = left[max(0, L-i) : min(L, L+R-i)],  b = right[max(0, i-L) : min(R, i)]  (equal lengths),
+ *       matches = #{k : a[k] == b[k]},  score = matches / i + i / 10000.0 in float64 (a division, a division, an addition);
+ *     the diagonal with the greatest score among those with matches > 1 wins, the smaller i among equal scores;
+ *     none: left_mid = L, right_mid = 0 (concatenation); else left_mid = (max(0, L-i) + min(L, L+R-i)) / 2 and
+ *     right_mid = (max(0, i-L) + min(R, i)) / 2 (integer halves);
+ *     left[:left_mid] goes to the output and left = right[right_mid:].
+ *   At the end `left` goes to the output.  The boundaries of a group are sequential; groups are independent.
+ *   ids int32 [rows, ld]; row r is ids[r, row_start[r] .. row_start[r] + row_len[r]) (row_start NULL = 0), 0 <= row_len[r]
+ *   <= max_row_len <= CA_CHUNK_MERGE_MAX_TOKENS and row_start[r] + row_len[r] <= ld; max_row_len is the caller's bound on
+ *   row_len (the lengths live on the device): above the limit the call returns CA_ERR_ARG and launches nothing.
+ *   skip: NULL, or a bitmap of skip_bits bits (uint32 words, bit id & 31 of word id >> 5): an id in [0, skip_bits) whose
+ *   bit is set is dropped while its row is loaded (any other id is kept); the rule above sees the rows without them.
+ *   group_off int32 [G + 1]: group g owns the rows group_off[g] .. group_off[g + 1] (a group may be empty: out_len 0).
+ *   out_off int32 [G + 1]: group g writes out[out_off[g] ..) and owns out_off[g + 1] - out_off[g] >= the sum of its
+ *   row_len (the merged length is never more); out_cap: the length of out.  out_len int32 [G].
+ *   cuts: NULL or int32 [rows, 2] = (left_mid, right_mid) of the boundary in front of every row, (-1, -1) for the first
+ *   row of a group.
+ *   A group whose offsets or rows are not as above gets out_len = -1 and touches no other memory (coral_amd/ops.py
+ *   checks them on the host first).  Exact integers and one fp64 score per diagonal, no atomics: bit-identical from run
+ *   to run.  One launch, one workgroup per group, no allocation, no synchronisation; bad arguments return CA_ERR_ARG
+ *   with the function's name in ca_last_error().
+ * ---------------------------------------------------------------------------------- */
+#define CA_CHUNK_MERGE_MAX_TOKENS 1024
+int ca_overlap_merge(const int32_t* ids, int64_t ld, const int32_t* row_start, const int32_t* row_len, int32_t rows,
+                     int32_t max_row_len, const uint32_t* skip, int32_t skip_bits, const int32_t* group_off,
+                     const int32_t* out_off, int32_t G, int32_t* out, int64_t out_cap, int32_t* out_len, int32_t* cuts,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Small elementwise pieces of the wav2vec2 encoder.
  * ca_mask_frames: SpecAugment + padding ($TF/.../modeling_wav2vec2.py:1272-1316, 752-755):
  *   h[b,t,:] = embed where tmask[b,t]; h[b,t,c] = 0 where fmask[b,c]; h[b,t,:] = 0 for

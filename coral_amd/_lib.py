@@ -151,6 +151,15 @@ class CaCtcBeamDesc(C.Structure):
                 ("ws", C.c_void_p), ("ws_bytes", C.c_int64)]
 
 
+class CaCtcBeamExt(C.Structure):
+    """Mirror of `CaCtcBeamExt` in include/coral_amd.h."""
+
+    _fields_ = ([("n_best", C.c_int32), ("hotword_weight", C.c_float)]
+                + [(n, C.c_void_p) for n in ("ids_n", "len_n", "score_n", "logit_n", "lm_n", "n_out",
+                                              "hot_keys", "hot_frac", "hot_word")]
+                + [("n_hot", C.c_int64)])
+
+
 class CaBeamDesc(C.Structure):
     """Mirror of `CaBeamDesc` in include/coral_amd.h."""
 
@@ -276,6 +285,7 @@ SIGNATURES = {
     "ca_ctc_collapse_offsets": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     "ca_ctc_beam_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "ca_ctc_beam_decode": (C.c_int, [C.POINTER(CaCtcBeamDesc), _vp]),
+    "ca_ctc_beam_decode_ex": (C.c_int, [C.POINTER(CaCtcBeamDesc), C.POINTER(CaCtcBeamExt), _vp]),
     "ca_ctc_align_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "ca_ctc_align": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32,
                                _vp]),

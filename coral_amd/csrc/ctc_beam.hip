@@ -33,6 +33,26 @@
 // set of survivors, every probability and the returned ids / score are bit-identical from run to run.  The slot a
 // survivor lands in may differ between runs; nothing observable depends on it.  LM look-ups are binary searches over
 // sorted 64-bit hashes in global memory.
+//
+// Extended entry (ca_ctc_beam_decode_ex, the EX = true instance of the same kernel; the plain entry is the EX = false
+// instance and compiles to what it was): n-best output and hotword boosting.
+//
+//   S_h(y) = S(y) + hotword_weight #{ w_i that are hotwords }
+//
+// The hotword table holds the open-word hash (WORD_SEED) of every prefix of every hotword, ascending, with the fraction
+// len / len_min (len_min: the shortest hotword with that prefix) and a flag "this prefix is itself a hotword".  A word
+// that closes (at a delimiter or after the last frame) adds hotword_weight when it is a hotword - beside, not instead
+// of, unk_score_offset when it is no LM unigram.  Ranking only: while the open word is a prefix of a hotword it adds
+// hotword_weight * fraction to the ranking score (a complete hotword that is still open: the full weight); the bonus is
+// gone once the open word is no hotword prefix, and is replaced by the exact term when the word closes.  A beam carries
+// its bonus (b_hot) and a flag bit; a candidate carries the table index in c_wid, which only delimiter candidates use
+// otherwise.  After the last frame every live prefix gets its S; a final's rank is the number of finals that beat it
+// under (S descending, prefix hash ascending) - counted, not sorted, so nothing depends on arrival order - and thread r
+// walks the (parent, symbol) nodes of the rank-r final.  score = logit_score + lm_score exactly: logit_score is
+// ln(p_b + p_nb), lm_score everything else, and S is formed as that fp32 sum.  Rank 0 is the plain entry's answer.
+//
+// Static LDS: 118 816 B for EX = false (as before), 119 840 B (117.0 KiB of the CU's 160 KiB) for EX = true: b_hot adds
+// 1 KiB; the final ranking reuses s_pb / s_pnb / merge_s / slot_s.
 #include "common.h"
 
 #define NEG_INF (-__builtin_inff())
@@ -85,6 +105,11 @@ __device__ __forceinline__ int64_t beam_bsearch(const uint64_t* __restrict__ key
   return -1;
 }
 
+// open-word hash -> index in the hotword table, or -1 (no prefix of any hotword)
+__device__ __forceinline__ int beam_hot_lookup(const CaCtcBeamExt& x, uint64_t h) {
+  return (int)beam_bsearch(x.hot_keys, 0, x.n_hot, h);
+}
+
 // open-word hash -> word id (>= 0), -1 (proper prefix of a unigram only), -2 (no prefix of any unigram)
 __device__ __forceinline__ int beam_word_lookup(const CaCtcBeamDesc& d, uint64_t h) {
   const int64_t i = beam_bsearch(d.pfx_keys, 0, d.n_pfx, h);
@@ -114,17 +139,20 @@ __device__ float beam_lm_logp(const CaCtcBeamDesc& d, const int* ctx, int n, int
 }
 
 // flags word of a beam: bits 0-8 last symbol + 1 (0 = empty prefix), 9 provisional-unk, 10 open word not empty,
-// 11-13 LM context length
+// 11-13 LM context length, 14 open word is a prefix of a hotword (EX only)
 #define FL_LAST(f) (((f) & 511) - 1)
 #define FL_PEN(f) (((f) >> 9) & 1)
 #define FL_OPEN(f) (((f) >> 10) & 1)
 #define FL_NCTX(f) (((f) >> 11) & 7)
+#define FL_HOT(f) (((f) >> 14) & 1)
 #define FL_MAKE(last, pen, open, nctx) (((last) + 1) | ((pen) << 9) | ((open) << 10) | ((nctx) << 11))
 
 // score of closing the open word of a beam with context ctx[0..n): returns the addend, the word id that enters the
-// context (-1: none, context cleared) in `w`
-__device__ __forceinline__ float beam_close_word(const CaCtcBeamDesc& d, bool have_lm, uint64_t ow, const int* ctx, int n,
-                                                 float alpha_ln10, int& w) {
+// context (-1: none, context cleared) in `w`.  EX: `hot` says that the open word is a prefix of a hotword; when it is
+// one itself, hotword_weight is added last.
+template <bool EX>
+__device__ __forceinline__ float beam_close_word(const CaCtcBeamDesc& d, const CaCtcBeamExt& x, bool have_lm, uint64_t ow,
+                                                 const int* ctx, int n, float alpha_ln10, bool hot, int& w) {
   float s = d.beta;
   w = -1;
   if (have_lm) {
@@ -136,6 +164,12 @@ __device__ __forceinline__ float beam_close_word(const CaCtcBeamDesc& d, bool ha
       w = wid;
     }
     if (w >= 0) s += alpha_ln10 * beam_lm_logp(d, ctx, n, w);
+  }
+  if constexpr (EX) {
+    if (hot) {
+      const int hi = beam_hot_lookup(x, ow);
+      if (hi >= 0 && x.hot_word[hi]) s += x.hotword_weight;
+    }
   }
   return s;
 }
@@ -153,15 +187,18 @@ __device__ __forceinline__ int beam_push_ctx(int* ctx, int n, int w, int order) 
   return cap;
 }
 
-__global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const CaCtcBeamDesc d) {
+template <bool EX>
+__global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const CaCtcBeamDesc d, const CaCtcBeamExt x) {
   __shared__ uint64_t b_hash[2][BEAM_MAX], b_ow[2][BEAM_MAX];
   __shared__ float b_pb[2][BEAM_MAX], b_pnb[2][BEAM_MAX], b_lm[2][BEAM_MAX];
   __shared__ int b_flags[2][BEAM_MAX], b_node[2][BEAM_MAX];
   __shared__ int b_ctx[2][BEAM_MAX][BEAM_CTX];
+  __shared__ float b_hot[EX ? 2 : 1][EX ? BEAM_MAX : 1];  // provisional hotword bonus of the open word (ranking only)
   __shared__ float s_pb[BEAM_MAX], s_pnb[BEAM_MAX], merge_s[BEAM_MAX];
   __shared__ int c_meta[BEAM_CAND_MAX];   // parent | symbol << 8 | provisional-unk << 16
   __shared__ float c_lm[BEAM_CAND_MAX];   // LM + bonus score of the extended prefix
-  __shared__ int c_wid[BEAM_CAND_MAX];    // word id entering the context at a delimiter (-1: none)
+  __shared__ int c_wid[BEAM_CAND_MAX];    // word id entering the context at a delimiter (-1: none); EX, other symbols:
+                                          // index of the open word in the hotword table (-1: no hotword prefix)
   __shared__ unsigned keys[BEAM_MAX + BEAM_CAND_MAX];  // [0, N) stays, [BEAM_MAX, BEAM_MAX + M) new prefixes
   __shared__ float lp_s[256];
   __shared__ int sym_s[256];
@@ -178,8 +215,9 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const CaCtcBeamD
   Tin = Tin > T ? T : (Tin < 0 ? 0 : Tin);
   const float* lg = d.logits + (int64_t)b * T * d.ldv;
   int2* trace = (int2*)d.ws + (int64_t)b * T * bw;  // node t * bw + slot -> (parent node, symbol)
-  int32_t* ids = d.ids_out + (int64_t)b * T;
-  for (int t = tid; t < T; t += BEAM_THREADS) ids[t] = -1;
+  const bool have_hot = EX && x.n_hot > 0;
+  int32_t* ids = EX ? x.ids_n + (int64_t)b * x.n_best * T : d.ids_out + (int64_t)b * T;
+  for (int64_t t = tid; t < (int64_t)(EX ? x.n_best : 1) * T; t += BEAM_THREADS) ids[t] = -1;
 
   int cur = 0, N = 1;
   if (tid == 0) {
@@ -195,6 +233,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const CaCtcBeamD
     }
     b_flags[0][0] = FL_MAKE(-1, 0, 0, nctx);
     b_node[0][0] = -1;
+    if constexpr (EX) b_hot[0][0] = 0.f;
   }
   __syncthreads();
 
@@ -285,17 +324,21 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const CaCtcBeamD
           int ctx[BEAM_CTX];
 #pragma unroll
           for (int q = 0; q < BEAM_CTX; ++q) ctx[q] = b_ctx[cur][i][q];
-          lm2 += beam_close_word(d, have_lm, b_ow[cur][i], ctx, FL_NCTX(fl), alpha_ln10, w);
+          lm2 += beam_close_word<EX>(d, x, have_lm, b_ow[cur][i], ctx, FL_NCTX(fl), alpha_ln10, FL_HOT(fl), w);
         }
       } else {
         pen2 = FL_PEN(fl);
         if (!pen2 && have_lm) pen2 = beam_word_lookup(d, beam_mix(b_ow[cur][i], c)) == -2;
+        // a longer word is a hotword prefix only if the word so far is one (or is empty)
+        if (have_hot && (!FL_OPEN(fl) || FL_HOT(fl))) w = beam_hot_lookup(x, beam_mix(b_ow[cur][i], c));
       }
       const int idx = atomicAdd(&ncand_s, 1);  // < N * nsym <= beam_width * (V - 1) <= BEAM_CAND_MAX
       c_meta[idx] = i | (c << 8) | (pen2 << 16);
       c_lm[idx] = lm2;
       c_wid[idx] = w;
-      keys[BEAM_MAX + idx] = beam_key(v + lm2 + (pen2 ? d.unk_score_offset : 0.f));
+      float rank = v + lm2 + (pen2 ? d.unk_score_offset : 0.f);
+      if constexpr (EX) rank += (c != d.delimiter && w >= 0) ? x.hotword_weight * x.hot_frac[w] : 0.f;
+      keys[BEAM_MAX + idx] = beam_key(rank);
     }
     __syncthreads();
     // ---- d. stays ----
@@ -307,7 +350,9 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const CaCtcBeamD
       const float npnb = beam_log_add2(last >= 0 ? pnb + lp_s[last] : NEG_INF, merge_s[tid]);
       s_pb[tid] = npb;
       s_pnb[tid] = npnb;
-      keys[tid] = beam_key(beam_log_add2(npb, npnb) + b_lm[cur][tid] + (FL_PEN(fl) ? d.unk_score_offset : 0.f));
+      float rank = beam_log_add2(npb, npnb) + b_lm[cur][tid] + (FL_PEN(fl) ? d.unk_score_offset : 0.f);
+      if constexpr (EX) rank += b_hot[cur][tid];
+      keys[tid] = beam_key(rank);
     }
     __syncthreads();
     const int K = BEAM_MAX + ncand_s;
@@ -409,6 +454,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const CaCtcBeamD
         b_node[nxt][slot] = b_node[cur][k];
 #pragma unroll
         for (int q = 0; q < BEAM_CTX; ++q) b_ctx[nxt][slot][q] = b_ctx[cur][k][q];
+        if constexpr (EX) b_hot[nxt][slot] = b_hot[cur][k];
       } else {
         const int idx = k - BEAM_MAX;
         const int meta = c_meta[idx];
@@ -431,7 +477,13 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const CaCtcBeamD
         b_pb[nxt][slot] = NEG_INF;
         b_pnb[nxt][slot] = lp_s[c] + (c == FL_LAST(fl) ? pb : beam_log_add2(pb, pnb));
         b_lm[nxt][slot] = c_lm[idx];
-        b_flags[nxt][slot] = FL_MAKE(c, pen2, open, nctx);
+        int flags = FL_MAKE(c, pen2, open, nctx);
+        if constexpr (EX) {
+          const int hi = open ? c_wid[idx] : -1;
+          b_hot[nxt][slot] = hi >= 0 ? x.hotword_weight * x.hot_frac[hi] : 0.f;
+          flags |= (hi >= 0) << 14;
+        }
+        b_flags[nxt][slot] = flags;
 #pragma unroll
         for (int q = 0; q < BEAM_CTX; ++q) b_ctx[nxt][slot][q] = ctx[q];
         const int node = t * bw + slot;
@@ -455,13 +507,57 @@ __global__ __launch_bounds__(BEAM_THREADS) void ctc_beam_kernel(const CaCtcBeamD
     float lm = b_lm[cur][tid];
     if (FL_OPEN(fl)) {
       int w;
-      lm += beam_close_word(d, have_lm, b_ow[cur][tid], ctx, nctx, alpha_ln10, w);
+      lm += beam_close_word<EX>(d, x, have_lm, b_ow[cur][tid], ctx, nctx, alpha_ln10, FL_HOT(fl), w);
       if (have_lm) nctx = beam_push_ctx(ctx, nctx, w, order);
     }
     if (have_lm && d.score_boundary && d.eos_wid >= 0) lm += alpha_ln10 * beam_lm_logp(d, ctx, nctx, d.eos_wid);
-    s_pb[tid] = beam_log_add2(b_pb[cur][tid], b_pnb[cur][tid]) + lm;
+    const float logit = beam_log_add2(b_pb[cur][tid], b_pnb[cur][tid]);
+    s_pb[tid] = logit + lm;
+    if constexpr (EX) {
+      s_pnb[tid] = logit;
+      merge_s[tid] = lm;
+    }
   }
   __syncthreads();  // also orders this workgroup's trace stores before the walk below
+  if constexpr (EX) {
+    // ---- n-best: rank by counting, one thread per returned hypothesis walks its nodes ----
+    const int nb = x.n_best;
+    int nfin = 0;
+    if (tid < BEAM_MAX) {
+      const unsigned mk = tid < N ? beam_key(s_pb[tid]) : 0u;
+      const uint64_t mh = tid < N ? b_hash[cur][tid] : 0ull;
+      int rank = 0;
+      for (int j = 0; j < N; ++j) {
+        const unsigned k = beam_key(s_pb[j]);
+        nfin += k != 0u;
+        rank += k != 0u && (k > mk || (k == mk && b_hash[cur][j] < mh));
+      }
+      if (mk != 0u && rank < nb) slot_s[rank] = tid;  // live beams have distinct prefix hashes, so ranks are distinct
+    }
+    __syncthreads();
+    if (tid < nb) {
+      const int64_t o = (int64_t)b * nb + tid;
+      if (tid < nfin) {
+        const int i = slot_s[tid];
+        int32_t* row = ids + (int64_t)tid * T;
+        int len = 0;
+        for (int node = b_node[cur][i]; node >= 0 && len < T; node = trace[node].x) ++len;
+        int pos = len;
+        for (int node = b_node[cur][i]; node >= 0 && pos > 0; node = trace[node].x) row[--pos] = trace[node].y;
+        x.len_n[o] = len;
+        x.score_n[o] = s_pb[i];
+        x.logit_n[o] = s_pnb[i];
+        x.lm_n[o] = merge_s[i];
+      } else {
+        x.len_n[o] = -1;
+        x.score_n[o] = NEG_INF;
+        x.logit_n[o] = NEG_INF;
+        x.lm_n[o] = NEG_INF;
+      }
+    }
+    if (tid == 0) x.n_out[b] = nfin < nb ? nfin : nb;
+    return;
+  }
   if (tid == 0) {
     int best = -1;
     unsigned bk = 0u;
@@ -490,10 +586,11 @@ extern "C" int64_t ca_ctc_beam_workspace_bytes(int32_t B, int32_t T, int32_t V, 
   return (((int64_t)B * T * beam_width * (int64_t)sizeof(int2)) + 255) & ~(int64_t)255;
 }
 
-extern "C" int ca_ctc_beam_decode(const CaCtcBeamDesc* desc, void* stream) {
+// the checks both entries share; `ext` decides which outputs must be there
+static int beam_check(const CaCtcBeamDesc* desc, const CaCtcBeamExt* ext) {
   CA_CHECK_ARG(desc, "ca_ctc_beam_decode: null descriptor");
   const CaCtcBeamDesc& d = *desc;
-  CA_CHECK_ARG(d.logits && d.ids_out && d.out_len && d.score_out && d.ws, "ca_ctc_beam_decode: null pointer");
+  CA_CHECK_ARG(d.logits && (ext || (d.ids_out && d.out_len && d.score_out)) && d.ws, "ca_ctc_beam_decode: null pointer");
   CA_CHECK_ARG(d.B > 0 && d.T > 0 && d.V >= 2 && d.V <= 256 && d.ldv >= d.V,
                "ca_ctc_beam_decode: bad shape (2 <= V <= 256)");
   CA_CHECK_ARG(d.blank >= 0 && d.blank < d.V && d.delimiter >= -1 && d.delimiter < d.V && d.delimiter != d.blank,
@@ -520,7 +617,34 @@ extern "C" int ca_ctc_beam_decode(const CaCtcBeamDesc* desc, void* stream) {
                "ca_ctc_beam_decode: pruning thresholds must be numbers (beam_prune_logp <= 0, -inf = off)");
   CA_CHECK_ARG(d.ws_bytes >= ca_ctc_beam_workspace_bytes(d.B, d.T, d.V, d.beam_width),
                "ca_ctc_beam_decode: workspace too small");
-  hipLaunchKernelGGL(ctc_beam_kernel, dim3(d.B), dim3(BEAM_THREADS), 0, (hipStream_t)stream, d);
+  return CA_OK;
+}
+
+extern "C" int ca_ctc_beam_decode(const CaCtcBeamDesc* desc, void* stream) {
+  if (const int rc = beam_check(desc, nullptr)) return rc;
+  CaCtcBeamExt none = {};
+  hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3(desc->B), dim3(BEAM_THREADS), 0, (hipStream_t)stream, *desc, none);
   CA_CHECK_LAUNCH("ca_ctc_beam_decode");
+  return CA_OK;
+}
+
+extern "C" int ca_ctc_beam_decode_ex(const CaCtcBeamDesc* desc, const CaCtcBeamExt* ext, void* stream) {
+  CA_CHECK_ARG(ext, "ca_ctc_beam_decode_ex: null extension");
+  if (const int rc = beam_check(desc, ext)) return rc;
+  CaCtcBeamExt x = *ext;
+  CA_CHECK_ARG(x.n_best >= 1 && x.n_best <= desc->beam_width, "ca_ctc_beam_decode_ex: n_best %d outside 1..beam_width = %d",
+               x.n_best, desc->beam_width);
+  CA_CHECK_ARG(x.ids_n && x.len_n && x.score_n && x.logit_n && x.lm_n && x.n_out,
+               "ca_ctc_beam_decode_ex: null output pointer");
+  CA_CHECK_ARG((int64_t)x.n_best * desc->T < ((int64_t)1 << 31), "ca_ctc_beam_decode_ex: n_best x T too large");
+  CA_CHECK_ARG(x.n_hot >= 0, "ca_ctc_beam_decode_ex: negative hotword table size");
+  CA_CHECK_ARG(x.n_hot > 0 || !(x.hot_keys || x.hot_frac || x.hot_word),
+               "ca_ctc_beam_decode_ex: hotword table pointers without a count");
+  CA_CHECK_ARG(x.n_hot == 0 || (x.hot_keys && x.hot_frac && x.hot_word),
+               "ca_ctc_beam_decode_ex: %lld hotword prefixes without their tables", (long long)x.n_hot);
+  CA_CHECK_ARG(x.hotword_weight - x.hotword_weight == 0.f, "ca_ctc_beam_decode_ex: hotword_weight must be a finite number");
+  if (x.hotword_weight == 0.f) x.n_hot = 0;  // "no hotwords": the search the plain entry runs
+  hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3(desc->B), dim3(BEAM_THREADS), 0, (hipStream_t)stream, *desc, x);
+  CA_CHECK_LAUNCH("ca_ctc_beam_decode_ex");
   return CA_OK;
 }

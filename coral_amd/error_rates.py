@@ -214,6 +214,36 @@ def batch_scores(predictions: list, labels: list, normalise: bool = False, devic
     return dict(cer=_rate(cc, normalise), wer=_rate(wc, normalise), char_counts=cc, word_counts=wc)
 
 
+def oracle_choice(counts, sizes) -> np.ndarray:
+    """counts int [sum(sizes), 4] (H, S, D, I) of every example's hypotheses in rank order, sizes[i] >= 1 of them for
+    example i -> int64 [n]: per example the position (inside its list) of the hypothesis with the fewest errors
+    S + D + I; ties go to the better-ranked one."""
+    c = np.asarray(counts, dtype=np.int64).reshape(-1, 4)
+    sizes = np.asarray(sizes, dtype=np.int64)
+    if (sizes < 1).any() or int(sizes.sum()) != len(c):
+        raise ValueError(f"oracle_choice: {len(c)} counts for lists of {sizes.tolist()} hypotheses (each at least one)")
+    err = c[:, 1] + c[:, 2] + c[:, 3]
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    return np.array([int(np.argmin(err[a:b])) for a, b in zip(off[:-1], off[1:])], dtype=np.int64)  # argmin: first minimum
+
+
+def oracle_counts(nbest_texts: list, labels: list, unit: str = "char", device="cuda") -> dict:
+    """The oracle error counts of n-best lists: how good the best hypothesis in each list is.  nbest_texts: per example
+    its hypotheses, best-ranked first (an empty list counts as the one hypothesis ""); all the (hypothesis, label) pairs
+    of the batch go through one ca_edit_counts launch.  -> {"counts": int64 [n, 4] of the chosen hypotheses, "index":
+    int64 [n] their positions (-1 for an empty list)}; the choice is `oracle_choice`."""
+    if len(nbest_texts) != len(labels):
+        raise ValueError(f"{len(nbest_texts)} n-best lists for {len(labels)} labels")
+    lists = [list(h) or [""] for h in nbest_texts]
+    sizes = [len(h) for h in lists]
+    flat = [t for h in lists for t in h]
+    counts = error_counts(flat, [l for l, n in zip(labels, sizes) for _ in range(n)], unit, device)
+    pick = oracle_choice(counts, sizes) if len(lists) else np.zeros(0, dtype=np.int64)
+    off = np.concatenate([[0], np.cumsum(sizes)])[:-1].astype(np.int64)
+    index = np.where(np.array([len(h) > 0 for h in nbest_texts], dtype=bool), pick, -1) if len(lists) else pick
+    return dict(counts=counts[off + pick] if len(lists) else counts, index=index)
+
+
 # ---- bootstrapped rates (ca_bootstrap_sums, coral_amd/csrc/bootstrap.hip) ----
 # The reference's model cards publish every CER / WER as "the mean of 1000 bootstrap resamples ± a 95 % confidence
 # interval"; the procedure itself is not in the reference tree, so parity with it is unpinned.  This project's reading:

@@ -31,7 +31,8 @@ WHISPER_CHUNK_LENGTH_REFUSAL = (
 
 
 def transcribe(model, processor, arrays: list, batch_size: int = 16, chunk_length_s: float = 0, stride_length_s=None,
-               return_timestamps=None, timestamp_source: str = "emission", sampling_rate=None):
+               return_timestamps=None, timestamp_source: str = "emission", sampling_rate=None, n_best=None, hotwords=None,
+               hotword_weight: float = 10.0):
     """ASR-pipeline equivalent ($TF/pipelines/automatic_speech_recognition.py:345,569-575,679):
     feature-extract, forward, argmax over all frames, CTC collapse, decode.  -> list of texts.
     chunk_length_s > 0: overlapping chunks with the pipeline's `chunk_length_s` / `stride_length_s` semantics
@@ -41,20 +42,27 @@ def transcribe(model, processor, arrays: list, batch_size: int = 16, chunk_lengt
     `ca_ctc_collapse_offsets`.  timestamp_source="alignment": the times come from the CTC forced alignment of the decoded
     ids to the same logits (`ca_ctc_align`) - with the greedy decoder and with the LM-fused beam search alike.
     sampling_rate: the rate of `arrays`, one int or one per recording (None: the extractor's).  Recordings at another
-    rate are resampled on the GPU first (coral_amd/resample.py), so chunking and times see audio at the model's rate."""
+    rate are resampled on the GPU first (coral_amd/resample.py), so chunking and times see audio at the model's rate.
+    n_best, hotwords, hotword_weight: the arguments of those names of `Wav2Vec2ProcessorWithLM.batch_decode` (LM decoding
+    only).  hotwords: words or phrases whose words each add hotword_weight to a hypothesis.  n_best: the
+    result per recording is {"text", "n_best": [{"text", "score", "logit_score", "lm_score", "posterior"}]} (+ "chunks"
+    with timestamps, which are the first hypothesis'); "text" is the first hypothesis, what the call returns without
+    n_best.  Refused by name: either argument with a processor without an LM, and n_best > beam_width."""
     from .longform import align_rows, check_timestamp_mode, collapse_rows, decode_rows, transcribe_long
+    from .nbest import check_nbest_arguments, lm_decode, nbest_records
     from .resample import to_rate
 
     with_lm = getattr(processor, "lm", None) is not None
     check_timestamp_mode(return_timestamps, with_lm, timestamp_source)
+    check_nbest_arguments(processor, n_best, hotwords, hotword_weight)
     if chunk_length_s is not None and chunk_length_s < 0:
         raise ValueError(f"chunk_length_s must be 0 (whole clips) or positive, got {chunk_length_s}")
     if sampling_rate is not None:
         arrays = to_rate(arrays, sampling_rate, processor.feature_extractor.sampling_rate, model.engine.device)
     if chunk_length_s:
         res = transcribe_long(model, processor, arrays, chunk_length_s, stride_length_s, batch_size, return_timestamps,
-                              timestamp_source)
-        return res if return_timestamps is not None else [r["text"] for r in res]
+                              timestamp_source, n_best=n_best, hotwords=hotwords, hotword_weight=hotword_weight)
+        return res if return_timestamps is not None or n_best is not None else [r["text"] for r in res]
     model.eval()
     out = []
     for i in range(0, len(arrays), batch_size):
@@ -65,11 +73,17 @@ def transcribe(model, processor, arrays: list, batch_size: int = 16, chunk_lengt
         eng = model.engine
         T = eng._saved["w"]["T"]
         if with_lm:  # Wav2Vec2ProcessorWithLM: LM-fused beam search on the GPU
-            ids, _ = eng.beam_decode(processor.device_tables(eng.device), tokenizer=processor.tokenizer,
-                                     **processor.decoder_params)
+            ids, hyps = lm_decode(eng, processor, n_best, hotwords, hotword_weight)
             if return_timestamps is not None:  # (timestamp_source="alignment": the check above refuses the other)
-                out += decode_rows(align_rows(eng, ids), processor.tokenizer, return_timestamps,
-                                   math.prod(eng.s.conv_stride), processor.feature_extractor.sampling_rate)
+                res = decode_rows(align_rows(eng, ids), processor.tokenizer, return_timestamps,
+                                  math.prod(eng.s.conv_stride), processor.feature_extractor.sampling_rate)
+            elif hyps is not None:
+                res = [{"text": processor.tokenizer.decode(r, group_tokens=False)} for r in ids]
+            if hyps is not None:
+                for item, h in zip(res, hyps):
+                    item["n_best"] = nbest_records(h, processor.tokenizer)
+            if return_timestamps is not None or hyps is not None:
+                out += res
                 continue
         elif T > 4096 or return_timestamps is not None:
             # every frame of the padded batch, as the greedy kernel below decodes them: identity segments
@@ -344,6 +358,9 @@ def evaluate(config, examples: list | None = None) -> dict:
         raise ValueError(f"whisper_long_form must be sequential or chunked, got {long_form!r}")
     if mtype == "whisper" and chunk_length_s > 0 and long_form != "chunked":
         raise ValueError(WHISPER_CHUNK_LENGTH_REFUSAL)
+    if mtype == "whisper" and (config.get("n_best", None) is not None or config.get("hotwords", None) is not None):
+        raise ValueError("n_best / hotwords belong to the LM-fused CTC beam search of wav2vec2 models; a Whisper model has "
+                         "neither (num_beams is its beam search)")
     if mtype == "whisper" and long_form == "chunked":  # what the mode refuses, before the model is loaded
         from .chunked_whisper import check_chunked_arguments
 
@@ -363,7 +380,7 @@ def evaluate(config, examples: list | None = None) -> dict:
     # `no_lm` (R/src/coral/evaluate.py:123-158): false decodes with model_dir/language_model/ when there is one
     saved = setup.load_saved() if mtype == "whisper" else setup.load_saved(no_lm=bool(config.get("no_lm", False)))
     model, processor = saved.model, saved.processor
-    id_rows = timed = None
+    id_rows = timed = nbest = None
     rates = None  # one per example when any of them names a rate
     if examples is not None and any(e.get("sampling_rate") is not None for e in examples):
         rates = [e.get("sampling_rate") for e in examples]
@@ -397,9 +414,18 @@ def evaluate(config, examples: list | None = None) -> dict:
             examples = [dict(audio=ex["input_values"], text=ex["text"])
                         for ex in synthetic_examples(processor, 2 * config.batch_size, 99, config.min_seconds_per_example,
                                                      min(3.0, config.max_seconds_per_example), config.sampling_rate)]
+        n_best = config.get("n_best", None)
+        hotwords = config.get("hotwords", None)
+        extra = {}  # n_best: null and hotwords: null leave the call, and every output below, as they are without the keys
+        if n_best is not None or hotwords is not None:
+            weight = config.get("hotword_weight", None)
+            extra = dict(n_best=None if n_best is None else int(n_best), hotwords=None if hotwords is None else list(hotwords),
+                         hotword_weight=10.0 if weight is None else float(weight))
         preds = transcribe(model, processor, [e["audio"] for e in examples], config.batch_size,
                            chunk_length_s=chunk_length_s, stride_length_s=config.get("stride_length_s", None),
-                           timestamp_source=config.get("timestamp_source", "emission"), sampling_rate=rates)
+                           timestamp_source=config.get("timestamp_source", "emission"), sampling_rate=rates, **extra)
+        if n_best is not None:
+            nbest, preds = [p["n_best"] for p in preds], [p["text"] for p in preds]
     preds = [p.lower().strip() for p in preds]
     labels = [e["text"].lower().strip() if config.lower_case else e["text"].strip() for e in examples]
     scores = dict(model_type=mtype, n=len(examples))
@@ -409,6 +435,13 @@ def evaluate(config, examples: list | None = None) -> dict:
         res = batch_scores(preds, labels, normalise, device)
         scores.update(cer=res["cer"], wer=res["wer"],
                       error_counts=dict(char=res["char_counts"].sum(0).tolist(), word=res["word_counts"].sum(0).tolist()))
+        if nbest is not None:  # how good the best hypothesis in each list is; the hypotheses normalised like the predictions
+            from .error_rates import _rate, oracle_counts
+
+            texts = [[h["text"].lower().strip() for h in hyps] for hyps in nbest]
+            oc, ow = oracle_counts(texts, labels, "char", device), oracle_counts(texts, labels, "word", device)
+            scores.update(oracle_cer=_rate(oc["counts"], normalise), oracle_wer=_rate(ow["counts"], normalise),
+                          oracle_index=dict(char=oc["index"].tolist(), word=ow["index"].tolist()))
         if boot is not None:  # the published form: mean ± half_width of the resampled rates (ca_bootstrap_sums)
             if boot_cluster is not None:
                 missing = [i for i, e in enumerate(examples) if boot_cluster not in e]
@@ -440,6 +473,15 @@ def evaluate(config, examples: list | None = None) -> dict:
                 w.writerow(["prediction", "label"])
                 w.writerows(zip(preds, labels))
         scores["csv"] = str(path)
+    if config.store_results and nbest is not None:
+        import json
+
+        with Path(f"{name}.nbest.jsonl").open("w", encoding="utf-8") as f:
+            for label, hyps in zip(labels, nbest):
+                f.write(json.dumps(dict(label=label, n_best=hyps), ensure_ascii=False) + "\n")
+        scores["nbest_jsonl"] = f"{name}.nbest.jsonl"
+    if nbest is not None:
+        scores["n_best"] = nbest
     if id_rows is not None:
         scores["token_ids"] = id_rows
     if timed is not None:

@@ -232,18 +232,22 @@ def stitch_long(model, arrays: list, chunk_length_s: float, stride_length_s=None
 
 
 def transcribe_long(model, processor, arrays: list, chunk_length_s: float, stride_length_s=None, batch_size: int = 16,
-                    return_timestamps=None, timestamp_source: str = "emission") -> list[dict]:
+                    return_timestamps=None, timestamp_source: str = "emission", n_best=None, hotwords=None,
+                    hotword_weight: float = 10.0) -> list[dict]:
     """Chunked wav2vec2 transcription with the pipeline's semantics -> [{"text": str}] plus, with
     return_timestamps="char" | "word", "chunks": [{"text", "timestamp": (start_s, stop_s)}] per recording.
     With a `Wav2Vec2ProcessorWithLM` the stitched logits go to the LM-fused beam search (no emission frames there).
     timestamp_source="alignment": the times are those of the CTC forced alignment of the decoded ids (greedy or beam) to
-    the stitched logits (`ca_ctc_align`), which serves both decoders."""
+    the stitched logits (`ca_ctc_align`), which serves both decoders.  n_best / hotwords / hotword_weight: as in
+    `evaluate.transcribe` (LM decoding only); with n_best every result carries "n_best"."""
+    from .nbest import check_nbest_arguments, lm_decode, nbest_records
     from .wav2vec2 import Wav2Vec2CTCEngine
 
     if not isinstance(getattr(model, "engine", None), Wav2Vec2CTCEngine):
         raise ValueError("chunk_length_s > 0 is built for wav2vec2 (CTC) models only: Whisper long-form decoding is not")
     with_lm = getattr(processor, "lm", None) is not None
     check_timestamp_mode(return_timestamps, with_lm, timestamp_source)
+    check_nbest_arguments(processor, n_best, hotwords, hotword_weight)
     if not arrays:
         return []
     eng = model.engine
@@ -251,11 +255,15 @@ def transcribe_long(model, processor, arrays: list, chunk_length_s: float, strid
     aligned = return_timestamps is not None and timestamp_source == "alignment"
     st = stitch_long(model, arrays, chunk_length_s, stride_length_s, batch_size, sr, want_logits=with_lm or aligned)
     if with_lm:
-        ids, _ = eng.beam_decode(processor.device_tables(eng.device), tokenizer=processor.tokenizer, in_len=st["in_len"],
-                                 logits=st["logits"], **processor.decoder_params)
+        ids, hyps = lm_decode(eng, processor, n_best, hotwords, hotword_weight, in_len=st["in_len"], logits=st["logits"])
         if not aligned:
-            return [{"text": processor.tokenizer.decode(r, group_tokens=False)} for r in ids]
-        rows = align_rows(eng, ids, st["logits"], st["in_len"])
+            res = [{"text": processor.tokenizer.decode(r, group_tokens=False)} for r in ids]
+        else:
+            res = decode_rows(align_rows(eng, ids, st["logits"], st["in_len"]), processor.tokenizer, return_timestamps,
+                              st["align_to"], sr)
+        for item, h in zip(res, hyps or []):
+            item["n_best"] = nbest_records(h, processor.tokenizer)
+        return res
     else:
         rows = collapse_rows(st["raw"], st["in_len"], eng.s.pad_token_id)
         if aligned:

@@ -265,6 +265,51 @@ class NGramLM:
                     bos_wid=self.bos_id if self.order > 1 else -1, eos_wid=self.eos_id, unk_wid=self.unk_id)
 
 
+def hotword_set(hotwords) -> list[str]:
+    """The set H of DESIGN.md §8: every whitespace-separated word of every entry, lower-cased as the evaluation
+    lower-cases text, de-duplicated, in first-seen order.  None or an empty list: no hotwords."""
+    if isinstance(hotwords, str):
+        raise TypeError("hotwords is a list of strings, not one string")
+    seen: dict[str, None] = {}
+    for entry in hotwords or ():
+        for word in str(entry).lower().split():
+            seen.setdefault(word, None)
+    return list(seen)
+
+
+def hotword_tables(hotwords, tokenizer, device="cpu") -> dict:
+    """Flat tensors for `ops.ctc_beam_decode_ex`, in the pattern of pfx_keys / pfx_wid:
+      hot_keys: rolling hash (WORD_SEED, symbol ids) of every prefix of every hotword, sorted as unsigned (stored as the
+        int64 bit pattern);
+      hot_frac: fp32 len(prefix) / len(shortest hotword with that prefix);  hot_word: uint8 1 where the prefix is itself
+        a hotword.
+    A word with a character outside the tokenizer's alphabet raises ValueError naming the word and the character."""
+    import torch
+
+    vocab = tokenizer.get_vocab()
+    special = {"<s>", "</s>", "<unk>", "<pad>", getattr(tokenizer, "word_delimiter_token", "|")}
+    sym = {c: i for c, i in vocab.items() if len(c) == 1 and c not in special}
+    pfx: dict[int, list] = {}   # hash -> [symbol ids, len_min, is a hotword]
+    for word in hotword_set(hotwords):
+        for c in word:
+            if c not in sym:
+                raise ValueError(f"hotword {word!r}: the character {c!r} is not in the tokenizer's alphabet")
+        h, ids = WORD_SEED, ()
+        for n, c in enumerate(word):
+            h = mix64(h, sym[c])
+            ids += (sym[c],)
+            old = pfx.setdefault(h, [ids, len(word), False])
+            if old[0] != ids:
+                raise ValueError(f"hotword prefix hash collision between {old[0]} and {ids}")
+            old[1] = min(old[1], len(word))
+            old[2] = old[2] or n == len(word) - 1
+    hk = np.array(sorted(pfx), dtype=np.uint64)
+    frac = np.array([np.float32(len(pfx[int(h)][0])) / np.float32(pfx[int(h)][1]) for h in hk], dtype=np.float32)
+    flag = np.array([pfx[int(h)][2] for h in hk], dtype=np.uint8)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+    return dict(hot_keys=t(hk.view(np.int64)), hot_frac=t(frac), hot_word=t(flag))
+
+
 def find_language_model(model_dir: str | Path):
     """-> (path of `language_model/*.arpa` or None, a `.bin` was seen)."""
     lm_dir = Path(model_dir) / "language_model"

@@ -574,11 +574,8 @@ def ctc_beam_workspace_bytes(B, T, V, beam_width):
     return lib().ca_ctc_beam_workspace_bytes(B, T, V, beam_width)
 
 
-def ctc_beam_decode(logits, in_len, ids_out, out_len, score_out, ws, B, T, V, ldv, blank, delimiter, forbidden=None,
-                    tables=None, beam_width=100, alpha=0.5, beta=1.5, unk_score_offset=-10.0, token_min_logp=-5.0,
-                    beam_prune_logp=-10.0, score_boundary=True):
-    """CTC prefix beam search with optional n-gram LM fusion (ca_ctc_beam_decode).  `tables`: the dict of
-    `NGramLM.device_tables` on the logits' device, or None for no LM.  `forbidden`: uint8 [V] device mask or None."""
+def _ctc_beam_desc(logits, in_len, ids_out, out_len, score_out, ws, B, T, V, ldv, blank, delimiter, forbidden, tables,
+                   beam_width, alpha, beta, unk_score_offset, token_min_logp, beam_prune_logp, score_boundary):
     d = _lib.CaCtcBeamDesc()
     d.logits, d.ldv, d.in_len = _p(logits), ldv, _p(in_len)
     d.B, d.T, d.V, d.blank, d.delimiter = B, T, V, blank, delimiter
@@ -596,7 +593,35 @@ def ctc_beam_decode(logits, in_len, ids_out, out_len, score_out, ws, B, T, V, ld
     d.token_min_logp, d.beam_prune_logp, d.score_boundary = token_min_logp, beam_prune_logp, int(bool(score_boundary))
     d.ids_out, d.out_len, d.score_out = _p(ids_out), _p(out_len), _p(score_out)
     d.ws, d.ws_bytes = _p(ws), ws.numel() * _ELT[ws.dtype]
+    return d
+
+
+def ctc_beam_decode(logits, in_len, ids_out, out_len, score_out, ws, B, T, V, ldv, blank, delimiter, forbidden=None,
+                    tables=None, beam_width=100, alpha=0.5, beta=1.5, unk_score_offset=-10.0, token_min_logp=-5.0,
+                    beam_prune_logp=-10.0, score_boundary=True):
+    """CTC prefix beam search with optional n-gram LM fusion (ca_ctc_beam_decode).  `tables`: the dict of
+    `NGramLM.device_tables` on the logits' device, or None for no LM.  `forbidden`: uint8 [V] device mask or None."""
+    d = _ctc_beam_desc(logits, in_len, ids_out, out_len, score_out, ws, B, T, V, ldv, blank, delimiter, forbidden, tables,
+                       beam_width, alpha, beta, unk_score_offset, token_min_logp, beam_prune_logp, score_boundary)
     check(lib().ca_ctc_beam_decode(C.byref(d), _stream()), "ca_ctc_beam_decode")
+
+
+def ctc_beam_decode_ex(logits, in_len, ids_n, len_n, score_n, logit_n, lm_n, n_out, ws, B, T, V, ldv, blank, delimiter,
+                       forbidden=None, tables=None, n_best=1, hotwords=None, hotword_weight=10.0, beam_width=100, alpha=0.5,
+                       beta=1.5, unk_score_offset=-10.0, token_min_logp=-5.0, beam_prune_logp=-10.0, score_boundary=True):
+    """The same search with n-best output and hotword boosting (ca_ctc_beam_decode_ex).  ids_n int32 [B, n_best, T],
+    len_n int32 [B, n_best], score_n / logit_n / lm_n fp32 [B, n_best], n_out int32 [B].  `hotwords`: the dict of
+    `ngram.hotword_tables` on the logits' device, or None."""
+    d = _ctc_beam_desc(logits, in_len, None, None, None, ws, B, T, V, ldv, blank, delimiter, forbidden, tables,
+                       beam_width, alpha, beta, unk_score_offset, token_min_logp, beam_prune_logp, score_boundary)
+    x = _lib.CaCtcBeamExt()
+    x.n_best, x.hotword_weight = n_best, hotword_weight
+    x.ids_n, x.len_n, x.score_n, x.logit_n, x.lm_n, x.n_out = (_p(ids_n), _p(len_n), _p(score_n), _p(logit_n), _p(lm_n),
+                                                               _p(n_out))
+    if hotwords is not None and hotwords["hot_keys"].numel():
+        x.hot_keys, x.hot_frac, x.hot_word = _p(hotwords["hot_keys"]), _p(hotwords["hot_frac"]), _p(hotwords["hot_word"])
+        x.n_hot = hotwords["hot_keys"].numel()
+    check(lib().ca_ctc_beam_decode_ex(C.byref(d), C.byref(x), _stream()), "ca_ctc_beam_decode_ex")
 
 
 def ctc_align_workspace_bytes(B, T, Lmax):

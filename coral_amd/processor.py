@@ -160,9 +160,22 @@ class Wav2Vec2ProcessorWithLM(Wav2Vec2Processor):
             self._tables[key] = self.lm.device_tables(self.tokenizer, device)
         return self._tables[key]
 
+    def hotword_tables(self, hotwords, device) -> dict | None:
+        """The device tables of `ngram.hotword_tables` for a hotword list, cached per word set and device; None for no
+        hotwords.  (`hotwords=` of transformers' `Wav2Vec2ProcessorWithLM.batch_decode`.)"""
+        from .ngram import hotword_set, hotword_tables
+
+        words = tuple(hotword_set(hotwords))
+        if not words:
+            return None
+        key = ("hotwords", str(device), words)
+        if key not in self._tables:
+            self._tables[key] = hotword_tables(words, self.tokenizer, device)
+        return self._tables[key]
+
     def save_pretrained(self, model_dir):
         super().save_pretrained(model_dir)
-        lm_dir = Path(model_dir) / "language_model"
+        lm_dir =Path(model_dir) / "language_model"
         lm_dir.mkdir(parents=True, exist_ok=True)
         self.lm.write_arpa(lm_dir / f"{self.lm.order}gram.arpa")
         (lm_dir / "attrs.json").write_text(json.dumps(self.decoder_params, indent=2))

@@ -739,7 +739,8 @@ class Wav2Vec2CTCEngine(Engine):
         ids_c, olen_c = ids.cpu(), olen.cpu()
         return [ids_c[b, :int(olen_c[b])].tolist() for b in range(B)], raw
 
-    def beam_decode(self, lm=None, beam_width: int = 100, in_len=None, tokenizer=None, logits=None, **params):
+    def beam_decode(self, lm=None, beam_width: int = 100, in_len=None, tokenizer=None, logits=None, n_best: int = 1,
+                    hotwords=None, hotword_weight: float = 10.0, **params):
         """CTC prefix beam search on the logits of the last forward, fused with the n-gram LM `lm` (the device-table
         dict of `NGramLM.device_tables`, or an `NGramLM` together with `tokenizer`; None: no LM, for which
         alpha = beta = 0 is the plain CTC prefix beam search).  `params`: alpha, beta, unk_score_offset,
@@ -747,8 +748,12 @@ class Wav2Vec2CTCEngine(Engine):
         delimiter and the ids that are never emitted (<s>, </s>, <unk>); without it there are no word boundaries and
         nothing is forbidden.  `logits`: a contiguous fp32 device tensor [B, T, ld >= V] to decode instead of the last
         forward's (the stitched rows of coral_amd/longform.py).
-        -> (ids list per row, scores fp32 [B] = S(y))."""
-        from .ngram import DEFAULT_PARAMS
+        -> (ids list per row, scores fp32 [B] = S(y)).
+        n_best > 1 or hotwords other than None (a list of words or phrases, or the dict of `ngram.hotword_tables`; each word that closes
+        adds hotword_weight) go through `ca_ctc_beam_decode_ex` and return, per row, a list of at most
+        n_best {"ids", "score", "logit_score", "lm_score"}, best first; hotwords need `tokenizer`, with or without an LM.
+        An empty hotword list or hotword_weight = 0 is "no hotwords"."""
+        from .ngram import DEFAULT_PARAMS, hotword_tables
 
         V = self.s.vocab_size
         dev = self.device
@@ -778,10 +783,36 @@ class Wav2Vec2CTCEngine(Engine):
         if unknown:
             raise TypeError(f"beam_decode: unknown parameters {sorted(unknown)}")
         p = dict(DEFAULT_PARAMS, **params)
+        if not isinstance(n_best, int) or isinstance(n_best, bool) or not 1 <= n_best <= beam_width:
+            raise ValueError(f"beam_decode: n_best={n_best!r} must be an integer in 1..beam_width = {beam_width}")
+        if not isinstance(hotword_weight, (int, float)) or not math.isfinite(hotword_weight):
+            raise ValueError(f"beam_decode: hotword_weight={hotword_weight!r} must be a finite number")
+        extended = n_best != 1 or hotwords is not None  # what decides the return type: the arguments, not their values
+        if hotwords is not None and not isinstance(hotwords, dict):
+            if tokenizer is None:
+                raise ValueError("beam_decode: hotwords need the tokenizer that spells them (and names the word delimiter)")
+            hotwords = hotword_tables(hotwords, tokenizer, dev)
+        if hotwords is not None and (hotwords["hot_keys"].numel() == 0 or hotword_weight == 0):
+            hotwords = None
+        if hotwords is not None and delim < 0:
+            raise ValueError("beam_decode: hotwords need the tokenizer (word delimiter id)")
         forbidden = torch.zeros(V, dtype=torch.uint8)
         for i in never:
             if 0 <= i < V and i != blank:
                 forbidden[i] = 1
+        if extended:
+            ids = torch.empty(B, n_best, T, dtype=torch.int32, device=dev)
+            olen = torch.empty(B, n_best, dtype=torch.int32, device=dev)
+            split = torch.empty(3, B, n_best, dtype=torch.float32, device=dev)
+            n_out = torch.empty(B, dtype=torch.int32, device=dev)
+            ws = torch.empty(ops.ctc_beam_workspace_bytes(B, T, V, beam_width), dtype=torch.uint8, device=dev)
+            ops.ctc_beam_decode_ex(logits, in_len, ids, olen, split[0], split[1], split[2], n_out, ws, B, T, V, Vp, blank,
+                                   delim, forbidden.to(dev), lm, n_best=n_best, hotwords=hotwords,
+                                   hotword_weight=float(hotword_weight), beam_width=beam_width, **p)
+            ids_c, olen_c, split_c, n_c = ids.cpu(), olen.cpu(), split.cpu(), n_out.cpu()
+            return [[dict(ids=ids_c[b, r, :int(olen_c[b, r])].tolist(), score=float(split_c[0, b, r]),
+                          logit_score=float(split_c[1, b, r]), lm_score=float(split_c[2, b, r]))
+                     for r in range(int(n_c[b]))] for b in range(B)]
         ids = torch.empty(B, T, dtype=torch.int32, device=dev)
         olen = torch.empty(B, dtype=torch.int32, device=dev)
         score = torch.empty(B, dtype=torch.float32, device=dev)

@@ -633,6 +633,33 @@ typedef struct CaCtcBeamDesc {
 int64_t ca_ctc_beam_workspace_bytes(int32_t B, int32_t T, int32_t V, int32_t beam_width);
 int ca_ctc_beam_decode(const CaCtcBeamDesc* desc, void* stream);
 
+/* The same search with n-best output and hotword boosting (objective S_h and rules: ctc_beam.hip).  `desc`
+ * as above, except that ids_out / out_len / score_out are not used and may be NULL.
+ *   n_best 1..beam_width.  Per utterance the n_best best finals by S descending (ties: lower 64-bit prefix hash; a
+ *   prefix with S = -inf is never returned): ids_n int32 [B,n_best,T] (-1 padded), len_n int32 [B,n_best], score_n /
+ *   logit_n / lm_n fp32 [B,n_best] with score = logit + lm exactly (logit = ln(p_b + p_nb), lm = every other term),
+ *   n_out int32 [B] = how many rows are real; the others have length -1, scores -inf and ids -1.  Row 0 is what
+ *   ca_ctc_beam_decode returns when there are no hotwords.
+ *   Hotwords (coral_amd/ngram.py::hotword_tables): hot_keys uint64 [n_hot] ascending rolling hashes (the pfx_keys hash)
+ *   of every prefix of every hotword, hot_frac fp32 [n_hot] = len / len_min (len_min: the shortest hotword with that
+ *   prefix), hot_word uint8 [n_hot] = 1 where the prefix is itself a hotword.  n_hot = 0 with NULL tables, or
+ *   hotword_weight = 0: no hotwords.  hotword_weight must be finite. */
+typedef struct CaCtcBeamExt {
+  int32_t n_best;
+  float hotword_weight;
+  int32_t* ids_n;
+  int32_t* len_n;
+  float* score_n;
+  float* logit_n;
+  float* lm_n;
+  int32_t* n_out;
+  const uint64_t* hot_keys;
+  const float* hot_frac;
+  const uint8_t* hot_word;
+  int64_t n_hot;
+} CaCtcBeamExt;
+int ca_ctc_beam_decode_ex(const CaCtcBeamDesc* desc, const CaCtcBeamExt* ext, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * CTC forced alignment (coral_amd/ctc_align.py, Wav2Vec2CTCEngine.align; word times under LM decoding, where the
  * transformers pipeline offers return_timestamps="word" only, $TF/pipelines/automatic_speech_recognition.py): the
